@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — allreduce GB/s of the MI355X engine (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set up, warm up, time
+the K steps, write the outputs (--dump-outputs), print the line.  --full adds every
+secondary measurement (N = 1: the schedule form, the cache-resident rate, the W = 1
+hierarchical step, the host-staged rates, config 1, the tile-sum, the CPU baseline;
+N > 1: the xGMI arms, the link probe, the RCCL comparator, cli_config3, the CPU leg).
 
 A step is one allreduce of device-resident bf16 buckets:
   N = 1  BASELINE config 2: the 8x8 Swing BO allreduce of 64 virtual ranks x
@@ -11,16 +17,19 @@ A step is one allreduce of device-resident bf16 buckets:
          12-step schedule).  32 rotating bucket sets (1.3 GB, 5x the 256 MiB Infinity
          Cache) so every step streams from HBM; K < 100 steps are eager launches
          behind a spin kernel, K >= 100 replays of a captured HIP graph
-         (DESIGN.md §6); ms_per_step = the median of 5 repetitions / K.
-         Beside it: the tile-sum (k_add) at 256 MiB and 1 GiB with its own roofline.
+         (DESIGN.md §6); exactly K steps are timed, ms_per_step = their time / K.
+         The last timed step runs on a bucket set of its own whose contents depend on
+         its seed alone (the rotating sets are reduced in place over and over: their
+         values overflow); --dump-outputs DIR writes what that step left there.
+         --full, beside it: the tile-sum (k_add) at 256 MiB and 1 GiB with its own roofline.
   N > 1  weak scaling: every GPU holds its own 64 x 640 kB ranks (same set
          rotation); on-GPU tree reduce -> 2D Swing BO between the N GPUs (grid
          (2,2), (2,4), (4,8)) over RCCL/xGMI or peer-mapped windows, or the
          one-kernel hierarchical form -> back to the 64 ranks; the transport
          is the fastest one verified on the machine running it (exact sums and
          the reference's closed form, verify_transport), median of 3
-         repetitions; every xGMI arm (configs 3-5) is verified before it is
-         timed, and the CPU loopback of configs 3-5 is timed beside it.
+         repetitions; with --full every xGMI arm (configs 3-5) is verified
+         before it is timed, and the CPU loopback of configs 3-5 is timed beside it.
 value = bytes of all ranks' buckets allreduced per second, whole job (GB/s, 1e9).
 Rank 0 prints ONE JSON line.  See DESIGN.md §Measurement for every field.
 """
@@ -39,6 +48,8 @@ import subprocess  # noqa: E402
 import sys  # noqa: E402
 import threading  # noqa: E402
 import traceback  # noqa: E402
+
+import numpy as np  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -116,6 +127,37 @@ def cpu_baseline() -> dict:
 # the fused BO kernel the engine launches at config 2 (kernels.hip launch_tree_fused)
 FUSED_KERNEL = "k_tree_lds_lag<64>"
 
+# N = 1: up to GRAPH_MAX_STEPS timed steps are one HIP graph; more are replays of a
+# GRAPH_CHUNK_STEPS-step graph and one last graph with the rest (bench_single)
+GRAPH_MAX_STEPS, GRAPH_CHUNK_STEPS = 4000, 2000
+LAST_SET_SEED = 999         # the seed of the last timed step's bucket set (the rotating sets: 1000 + i)
+DUMP_SAMPLE_COLUMNS = 65536   # --dump-outputs: columns of every rank's row that are written (of 327,680)
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_sample_columns() -> np.ndarray:
+    """The fixed, seeded sample of element indices that --dump-outputs writes for every rank
+    (numpy's legacy generator: the same stream in every numpy version)"""
+    return np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).permutation(ELEMS)[:DUMP_SAMPLE_COLUMNS])
+
+
+def dump_outputs(path: str, bucket: torch.Tensor) -> None:
+    """--dump-outputs DIR: what the last timed step left in its bucket set, the 64 ranks'
+    allreduced rows a caller of the timed path receives (bf16, written as float32: exact):
+      allreduce_rank0.npy              rank 0's whole row, (327680,)
+      allreduce_ranks_sample.npy       every rank's row at the sampled columns, (64, 65536)
+      allreduce_sample_columns.npy     the sampled element indices, (65536,) float64
+    19 MB in all (the 64 whole rows would be 84 MB).  The step's inputs — the seeded set of
+    LAST_SET_SEED, allreduced once by the untimed lead-in — depend on the seed alone, so two
+    builds' files compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    rows = bucket[:, :ELEMS].view(torch.bfloat16)
+    cols = dump_sample_columns()
+    idx = torch.from_numpy(cols).to(bucket.device)
+    np.save(os.path.join(path, "allreduce_rank0.npy"), rows[0].float().cpu().numpy())
+    np.save(os.path.join(path, "allreduce_ranks_sample.npy"), rows[:, idx].float().cpu().numpy())
+    np.save(os.path.join(path, "allreduce_sample_columns.npy"), cols.astype(np.float64))
+
 
 def pmc_traffic(kernel: str):
     """HBM bytes per launch of `kernel` from the committed PMC summary
@@ -182,78 +224,153 @@ def bench_single(args) -> dict:
     sets = [torch.empty((RANKS, stride), dtype=torch.int16, device=dev) for _ in range(nsets)]
     for i, s in enumerate(sets):
         fill_reference_convention(s[:, :ELEMS], 1000 + i)
+    # The rotating sets are allreduced in place again and again (every pass multiplies their
+    # values by 64: they overflow during the prewarm), so the LAST timed step runs on a set of
+    # its own, put back to its seeded inputs (last_src) behind the warmup steps and allreduced
+    # once by the untimed lead-in: what the timed step leaves there is a function of the seed
+    # alone (--dump-outputs)
+    last_src = torch.zeros((RANKS, stride), dtype=torch.int16, device=dev)
+    fill_reference_convention(last_src[:, :ELEMS], LAST_SET_SEED)
+    last = last_src.clone()
     torch.cuda.synchronize()
     plan = t.Plan(t.SWING, t.BO, SIDE, ELEMS, RANKS, t.EXEC_FUSED)
-    steps_plan = t.Plan(t.SWING, t.BO, SIDE, ELEMS, RANKS, t.EXEC_STEPS)
 
     def step(i, p=plan):
         p.execute(sets[i % nsets].data_ptr(), stride, None, stream)
 
+    def run_steps(count, final):   # count steps over the rotating sets; final: the last of them on `last`
+        for i in range(count - final):
+            step(i)
+        if final:
+            plan.execute(last.data_ptr(), stride, None, stream)
+
     # How the K timed steps are issued (tools/timing_probe.py, profiles/r02_timing_methods.jsonl):
-    #   K >= 100: R back-to-back replays of a K-step HIP graph; each replay of a
-    #     ROCm graph starts with a fixed ~7 us of GPU-side launch latency, which
-    #     costs < 0.1 us per step here (K = 200: 14.02 us graph vs 14.14 eager);
+    #   K >= 100: one replay of a K-step HIP graph; a replay of a ROCm graph
+    #     starts with a fixed ~7 us of GPU-side launch latency, which
+    #     costs < 0.1 us per step here (K = 200: 14.02 us graph vs 14.14 eager).
+    #     Past GRAPH_MAX_STEPS the K steps are replays of one GRAPH_CHUNK_STEPS-step
+    #     graph and a last graph with the rest (the cost of capturing and
+    #     instantiating a graph grows with its nodes; 7 us in 2000 steps is nothing);
     #   K < 100: K eager launches behind a spin kernel that covers the host's
     #     submission (K = 20: 14.2-14.4 us vs 14.4-14.6 for graph replays).
-    # The graph is captured BEFORE the prewarm, so no host-only phase sits
+    # The graphs are captured BEFORE the prewarm, so no host-only phase sits
     # between the steady-clock prewarm and the timed steps.
-    use_graph = not args.eager and args.steps >= 100
-    graph = None
-    if use_graph:
+    K = args.steps
+    chunk = K if K <= GRAPH_MAX_STEPS else GRAPH_CHUNK_STEPS
+    n_body = (K - 1) // chunk      # timed replays of the chunk-step graph (0 up to GRAPH_MAX_STEPS)
+    n_tail = K - n_body * chunk    # steps of the last graph, 1 .. chunk; its last step runs on `last`
+    body = tail = None
+    if not args.eager and K >= 100:
         try:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                for i in range(args.steps):
-                    step(i)
+            tail = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(tail, stream=stream):
+                run_steps(n_tail, True)
+            if n_body:
+                body = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(body, stream=stream):
+                    run_steps(chunk, False)
             torch.cuda.synchronize()
         except Exception as e:  # fall back to eager launches, say so
             print(f"[bench] graph capture failed ({e}); eager launches", file=sys.stderr)
-            graph = None
+            body = tail = None
 
-    def k_steps():   # one pass over the K timed steps
+    def k_steps():   # the K timed steps, once
         with torch.cuda.stream(stream):
-            if graph is not None:
-                graph.replay()
+            if tail is not None:
+                for _ in range(n_body):
+                    body.replay()
+                tail.replay()
             else:
-                for i in range(args.steps):
-                    step(i)
+                run_steps(K, True)
+
+    def warm_graphs(i=0):   # every captured graph once, the last graph last (a graph's first replay uploads it)
+        if body is not None:
+            body.replay()
+        tail.replay()
 
     with torch.cuda.stream(stream):
-        prewarm_s = prewarm(lambda i: k_steps() if graph is not None else step(i), args.prewarm_ms,
-                            batch=max(1, 200 // args.steps) if graph is not None else 50)
+        prewarm_s = prewarm(warm_graphs if tail is not None else step, args.prewarm_ms,
+                            batch=max(1, 200 // K) if tail is not None else 50)
         for i in range(args.warmup):
             step(i)
+        last.copy_(last_src)   # the seeded inputs again (the prewarm's graph replays ran on `last` too)
     torch.cuda.synchronize()
 
-    # R repetitions of the K timed steps, an event between consecutive ones;
-    # ms_per_step = the median repetition / K (each interval is exactly K
-    # steps).  The whole R x K region is bracketed by synchronize on both sides.
-    reps = max(1, args.reps)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+    # Exactly K steps are timed, back to back, an event on either side;
+    # ms_per_step = that time / K.  The region is bracketed by synchronize on both sides.
+    # Behind the spin kernel an untimed lead-in runs first, issued exactly like the timed
+    # steps (the same graph replayed, or the same eager launches) with nothing but the
+    # event between them: the first pass behind another kind of kernel is slower (of 5
+    # back-to-back repetitions of the K steps the first took 0.5-1 % longer than the
+    # others in the recorded runs, profiles/r06_*bench*.json; a replay behind a copy
+    # kernel or behind another graph's replay as much).  The lead-in's last step runs on
+    # `last` as well, so the last timed step allreduces the allreduced seeded inputs:
+    # two passes over [0, 100) values stay finite (< 64 * 64 * 100) and depend on the seed alone.
+    reps = max(1, args.reps)   # --full: repetitions of the secondary measurements
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with torch.cuda.stream(stream):
-        # a spin kernel ahead of the first event keeps the GPU busy while the host
+        # a spin kernel ahead of the lead-in keeps the GPU busy while the host
         # submits (eager: ~4 us of host time per launch; host_wall_s below includes everything)
-        torch.cuda._sleep(max(200000, 15000 * args.steps * (1 if graph is not None else reps)))
-    ev[0].record(stream)
-    for r in range(reps):
-        k_steps()
-        ev[r + 1].record(stream)
+        torch.cuda._sleep(max(200000, 15000 * (K + chunk if tail is None else min(K, GRAPH_MAX_STEPS))))
+        if tail is not None:
+            warm_graphs()
+        else:
+            run_steps(chunk, True)
+    e0.record(stream)
+    k_steps()
+    e1.record(stream)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    rep_ms = [ev[r].elapsed_time(ev[r + 1]) for r in range(reps)]
-    ms_per_step = statistics.median(rep_ms) / args.steps
-    e0, e1 = ev[0], ev[1]
+    timed_ms = e0.elapsed_time(e1)
+    ms_per_step = timed_ms / K
     fused_launch = t.last_launch()   # the bench kernel's grid and residency (launched in the warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     bytes_all = RANKS * ELEMS * 2
-    steps_ms = hot_ms = float("nan")
     if args.main_only:  # profiling runs: nothing but the timed workload (+ warmup)
         plan.close()
-        steps_plan.close()
         return {"ms_per_step": ms_per_step, "value": bytes_all / (ms_per_step * 1e-3) / 1e9}
 
+    alg_bytes = 2 * RANKS * ELEMS * 2          # read every rank once, write every rank once
+    achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9
+    out = {
+        "metric": METRIC,
+        "value": round(bytes_all / (ms_per_step * 1e-3) / 1e9, 3),
+        "unit": "GB/s",
+        "n_gpus": 1,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 6),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic (uniform [0,100) bf16, reference rank convention); 32 rotating bucket sets in HBM (1.3 GB), "
+                "rank rows 655,360 B + 128 B skew; the last timed step on a set of its own (seeded inputs)",
+        "timing": {"method": "hip_graph_replays" if tail is not None else "eager_behind_spin_kernel",
+                   "timed_steps": K, "graph_replays": (n_body + 1) if tail is not None else 0,
+                   "ms_timed": round(timed_ms, 5), "untimed_lead_in_steps": chunk + (n_tail if body is not None else 0),
+                   "ms_per_step": "the time of the K timed steps (back to back, one HIP event on either side) / K"},
+        "config": {"workload": "BASELINE config 2: 8x8 Swing BO allreduce, 64 virtual ranks x 655,360 B bf16 "
+                               "(5 tiles/block) on one MI355X, fused one-pass HIP kernel, no RCCL",
+                   "ranks": RANKS, "bytes_per_rank": ELEMS * 2, "algo": "swing", "variant": "BO",
+                   "exec": "fused", "launches_per_step": plan.launches, "hip_graph": tail is not None},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": pmc_traffic(FUSED_KERNEL),
+                     "kernel": FUSED_KERNEL, "algorithmic_bytes_per_launch": alg_bytes, "launch": fused_launch},
+        "full": bool(args.full),
+        "prewarm_ms": round(prewarm_s * 1e3, 1),
+        "host_wall_s": round(wall, 6),
+    }
+    if not args.full:   # a plain run: the headline and nothing else
+        plan.close()
+        return out
+
+    steps_plan = t.Plan(t.SWING, t.BO, SIDE, ELEMS, RANKS, t.EXEC_STEPS)
+    steps_ms = hot_ms = float("nan")
     # schedule form (k_steps_reg: every RS / AG step of every rank in ONE persistent launch), same
     # buckets, timed like the headline's eager path: behind a spin kernel, R repetitions, median
     sched = timed_eager(stream, lambda: [step(i, steps_plan) for i in range(args.steps)], args.steps, reps)
@@ -384,32 +501,7 @@ def bench_single(args) -> dict:
 
     tsum = tilesum(stream, args.steps, reps)
 
-    alg_bytes = 2 * RANKS * ELEMS * 2          # read every rank once, write every rank once
-    achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9
-    out = {
-        "metric": METRIC,
-        "value": round(bytes_all / (ms_per_step * 1e-3) / 1e9, 3),
-        "unit": "GB/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 6),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic (uniform [0,100) bf16, reference rank convention); 32 rotating bucket sets in HBM (1.3 GB), "
-                "rank rows 655,360 B + 128 B skew",
-        "timing": {"method": "hip_graph_replays" if graph is not None else "eager_behind_spin_kernel",
-                   "repetitions": reps, "ms_per_repetition": [round(x, 5) for x in rep_ms],
-                   "ms_per_step": "median repetition / steps (each repetition = the K steps, back to back)"},
-        "config": {"workload": "BASELINE config 2: 8x8 Swing BO allreduce, 64 virtual ranks x 655,360 B bf16 "
-                               "(5 tiles/block) on one MI355X, fused one-pass HIP kernel, no RCCL",
-                   "ranks": RANKS, "bytes_per_rank": ELEMS * 2, "algo": "swing", "variant": "BO",
-                   "exec": "fused", "launches_per_step": plan.launches, "hip_graph": graph is not None},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": pmc_traffic(FUSED_KERNEL),
-                     "kernel": FUSED_KERNEL, "algorithmic_bytes_per_launch": alg_bytes, "launch": fused_launch},
+    out.update({
         "schedule_faithful": {"launches_per_step": steps_plan.launches, "ms_per_step": round(steps_ms, 6),
                               "value": round(bytes_all / (steps_ms * 1e-3) / 1e9, 3), **sched},
         "cache_resident": {"ms_per_step": round(hot_ms, 6), "value": round(bytes_all / (hot_ms * 1e-3) / 1e9, 3)},
@@ -419,9 +511,7 @@ def bench_single(args) -> dict:
         "host_staged": e2e,
         "config1": config1,
         "tilesum": tsum,
-        "prewarm_ms": round(prewarm_s * 1e3, 1),
-        "host_wall_s": round(wall, 6),
-    }
+    })
     plan.close()
     steps_plan.close()
     return out
@@ -1725,10 +1815,7 @@ def multi_line(args, world, transport, ms_per_step, local_ms, wall, extras) -> d
     }
 
 
-def main():
-    # RCCL and gloo print banners on stdout; keep stdout for the one JSON line
-    real_stdout = os.dup(1)
-    os.dup2(2, 1)
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -1738,9 +1825,18 @@ def main():
     ap.add_argument("--sets", type=int, default=32, help="rotating bucket sets (1.3 GB per GPU: far past the 256 MiB MALL)")
     ap.add_argument("--eager", action="store_true", help="no HIP graph capture")
     ap.add_argument("--reps", type=int, default=5,
-                    help="N = 1: back-to-back replays of the K timed steps; ms_per_step = median replay / K")
-    ap.add_argument("--no-cpu-baseline", dest="cpu", action="store_false")
-    ap.add_argument("--no-extras", dest="extras", action="store_false")
+                    help="repetitions of the K steps in the secondary measurements (--full) and at N > 1, "
+                         "median; the N = 1 headline times exactly K steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement (N = 1: schedule form, cache-resident rate, W = 1 "
+                         "hierarchical step, host-staged rates, config 1, tile-sum, CPU baseline; N > 1: xGMI "
+                         "arms, link probe, RCCL comparator, cli_config3, CPU leg); a plain run measures the "
+                         "headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed step computed to DIR/<name>.npy (float32, 19 MB; "
+                         "dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", dest="cpu", action="store_false", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", dest="extras", action="store_false", help="N > 1: --full without the extras")
     ap.add_argument("--peer-timeout", type=float, default=240.0,
                     help="N > 1: seconds the peer-window phase may take before the RCCL-measured line is printed")
     ap.add_argument("--extras-timeout", type=float, default=240.0,
@@ -1755,8 +1851,22 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="run the N>1 code path on one GPU (1-rank RCCL)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal: every rank on cuda:0, peer transports only (no RCCL); not a measurement")
+    return ap
+
+
+def main():
+    # RCCL and gloo print banners on stdout; keep stdout for the one JSON line
+    real_stdout = os.dup(1)
+    os.dup2(2, 1)
+    ap = arg_parser()
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline alone
+        args.extras = args.cpu = False
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (world > 1 or args.force_dist or args.tilesum_only is not None):
+        ap.error("--dump-outputs writes the N = 1 workload's outputs (--gpus 1)")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1 or args.force_dist:

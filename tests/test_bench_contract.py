@@ -27,6 +27,22 @@ def test_gpu_grids_map_onto_the_reference_2d_functions():
     assert bench.GRIDS[2] == (2, 2) and bench.GRIDS[4] == (2, 4) and bench.GRIDS[8] == (4, 8)
 
 
+def test_a_plain_run_is_the_headline_alone_and_full_is_opt_in():
+    """The driver's invocation (--gpus 1 --steps K --warmup W) measures the headline and
+    nothing else; --full turns the secondary measurements on, --dump-outputs names the
+    directory of the last timed step's outputs, whose sample is fixed by its seed."""
+    ap = bench.arg_parser()
+    a = ap.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.gpus, a.steps, a.warmup) == (1, 20, 5) and a.full is False and a.dump_outputs is None
+    a = ap.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out" and a.cpu is True and a.extras is True
+    cols = bench.dump_sample_columns()
+    assert cols.shape == (bench.DUMP_SAMPLE_COLUMNS,) and (cols == bench.dump_sample_columns()).all()
+    assert (cols[1:] > cols[:-1]).all() and 0 <= cols[0] and cols[-1] < bench.ELEMS
+    # float32 files: rank 0's row, every rank at the sample, the sample's indices (float64) — under 64 MB
+    assert 4 * bench.ELEMS + (4 * bench.RANKS + 8) * bench.DUMP_SAMPLE_COLUMNS <= 64 * 10 ** 6
+
+
 def test_n_gt_1_budget_skips_extras_before_the_deadline(monkeypatch):
     """The N > 1 line's wall-clock budget (verdict r05 item 2): a phase starts only
     while the time left covers max(60 s, 2 x the longest phase so far); skipped

@@ -96,7 +96,7 @@ def run_hung(phase: str, hard_s: int, how: str = "HANG"):
     env[f"ALLRED_BENCH_TEST_{how}_IN"] = phase
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--share-gpu", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"]
+           "--gpus", "2", "--share-gpu", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=hard_s + 120)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (p.stdout[-2000:], p.stderr[-3000:])

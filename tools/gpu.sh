@@ -111,7 +111,7 @@ EOF2
 share)
     n=${1:-2}
     timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus "$n" --share-gpu --steps 20 --warmup 5 \
+        --master-port 29533 bench.py --gpus "$n" --share-gpu --steps 20 --warmup 5 --full \
         > gpurun_out/share_n$n.json 2> gpurun_out/share_n$n.err
     rc=$?
     tail -5 gpurun_out/share_n$n.err
