@@ -27,7 +27,9 @@ extern "C" {
  * default), the tune keys hier_x2_tail / hier_x_lag / hier_x_chunked / hier_x_rearly /
  * hier_x_latepoll are gone (k_hier_x2 runs its measured product form only), and
  * allred_last_launch is new.  ABI 6 (round 5): the hierarchical forms' hand-off area holds
- * 6 data bytes + a 16-bit epoch per word — peers of different ABIs must not connect. */
+ * 6 data bytes + a 16-bit epoch per word — peers of different ABIs must not connect.
+ * Still ABI 7: allred_run_io, allred_validate_device and allred_rank_check are additions —
+ * no existing struct layout, signature or behaviour changes, so the version stays. */
 #define ALLRED_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------- */
@@ -173,6 +175,33 @@ int allred_tree_reduce(const uint16_t* ranks, uint64_t rank_stride, size_t n, in
                        int total_nodes, uint16_t* out, void* stream);
 int allred_broadcast(uint16_t* ranks, uint64_t rank_stride, size_t n, int total_nodes, const uint16_t* src,
                      void* stream);
+
+/* validate_result_vector (allred_helper.cpp:18-120) on the GPU, for `rows` device-resident
+ * rows at once (row r at ranks + r * rank_stride elements; pinned host rows through their
+ * device pointer work too): one launch of k_validate, which reads every row once and src0 /
+ * src1 once.  Per element expected = bf16((a + b) * mult) — the add, then the multiply, in
+ * fp32; the conversion truncates (round_mode 0) or rounds to nearest even (1) — diff =
+ * |actual - expected| in fp32, and the element is bad when !(diff <= error): NaN is bad, and so
+ * is inf - inf, exactly as on the host.  mult is the reference's (float)(total_nodes / 2), or
+ * any other closed form of the caller's.  Per row: bad = what allred_validate_result_vector
+ * returns for it; first_bad = the lowest bad element index (UINT64_MAX: none); max_error = the
+ * largest non-NaN diff over the bad elements (0: none).  The host function leaves the FIRST
+ * mismatch out of its maximum (a quirk of the reference's loop, allred_helper.cpp:49-75);
+ * this one does not, so the two maxima may differ by that one element.
+ * Enqueues on `stream` (counters zeroed by a stream-ordered memset, the launch, the copy of the
+ * `rows` records to out[], host memory) and returns once the records are on the host.
+ * ALLRED_ERR_ARG before any HIP call: a null pointer, n == 0 or n % 8 != 0, rows < 1 or
+ * rows > ALLRED_MAX_NODES, rank_stride < n or % 8 != 0, a pointer not 16-byte aligned.
+ * Nothing past element n of a row is read (the stride skew holds no data). */
+typedef struct {
+    uint64_t bad;
+    uint64_t first_bad;
+    float max_error;
+    int32_t reserved;
+} allred_rank_check;
+int allred_validate_device(const uint16_t* ranks, uint64_t rank_stride, size_t n, int rows, const uint16_t* src0,
+                           const uint16_t* src1, float mult, float error, int round_mode,
+                           allred_rank_check* out /*[rows], host*/, void* stream);
 
 /* ======================================================================
  * Virtual-rank plan: `total` ranks resident in ONE GPU's HBM, rank r at
@@ -366,6 +395,28 @@ typedef struct {
  * layout of tt-metal's profile_log_device.csv (the reference's
  * TT_METAL_DEVICE_PROFILER=1 run, python/timing_taker.py:60-65).            */
 int allred_run(const allred_args* args, int verbose, allred_report* report);
+/* allred_run with the data in the caller's hands (allred_run(a, v, r) is
+ * allred_run_io(a, v, r, NULL, NULL, NULL)):
+ *   in_all      NULL, or total * elems bf16 rank-major inputs of the caller's own (arbitrary
+ *               data: validation is skipped, report->mismatches = -1, as allred_run_multi);
+ *   out_all     NULL, or total * elems bf16 receiving every rank's result, rank-major;
+ *   result_vec  NULL, or num_els = elems / 2 packed words receiving print_core's result: the
+ *               reference's AllredConfig::result_vec (allred_helper.hpp:92).
+ * elems = num_tiles * 1024.  With run_kernel == 0 both receive the unreduced inputs.  A failed
+ * call writes neither.  args->gpus > 0 dispatches like allred_run (ALLRED_TRANSPORT /
+ * ALLRED_SHARE_GPU) and forwards the buffers to allred_run_multi: with ALLRED_TRANSPORT=host
+ * the whole call makes no HIP call.  On one GPU every end-to-end mode (ALLRED_E2E=zerocopy |
+ * dma, ALLRED_E2E_CHUNKS) gives the bits of the plan on the same data; with in_all the
+ * column-chunked DMA form runs only where a column chunk's pass is that bit for bit (schedules
+ * whose per-block trees coincide: every RecDub grid, Swing up to 16 ranks), else the buckets go
+ * as one copy each way.
+ * ALLRED_CHECK_ALL=device (one GPU): the ranks other than print_core are counted by
+ * allred_validate_device on the memory the result lives in (the device rows of the DMA modes,
+ * the pinned buckets through their device pointer in zero-copy mode) instead of N - 1 host
+ * passes; report->mismatches is the same number.  print_core still goes through the host
+ * validator and its printed report.  The multi-GPU path ignores `device`. */
+int allred_run_io(const allred_args* args, int verbose, allred_report* report, const uint16_t* in_all,
+                  uint16_t* out_all, uint32_t* result_vec);
 
 /* ======================================================================
  * Multi-GPU: one process per GPU, RCCL point-to-point over xGMI.

@@ -103,12 +103,30 @@ public:
         while ((1u << s) < TOTAL_NODES) ++s;
         SWING_ALGO_STEPS = s;
         num_els = (int)(single_tile_size * (uint32_t)NUM_TILES / sizeof(uint32_t));
+        // allred_helper.cpp:277-285: the two source vectors every core loads one of
+        // (TOTAL_NUM_TILES stays unassigned there too: declared, never written)
+        const std::size_t bytes = (std::size_t)single_tile_size * (std::size_t)NUM_TILES;
+        src_vec_0.resize((std::size_t)num_els);
+        if (RND_SRC < 0) {
+            allred_constant_bf16_vector(bytes, 1.0f, src_vec_0.data());
+            src_vec_1 = src_vec_0;
+            result_vec.resize((std::size_t)num_els);
+            allred_constant_bf16_vector(bytes, 0.0f, result_vec.data());
+        } else {
+            src_vec_1.resize((std::size_t)num_els);
+            allred_random_bf16_vector(bytes, 100, RND_SRC, args.round_mode, src_vec_0.data());
+            allred_random_bf16_vector(bytes, 100, RND_SRC + 1, args.round_mode, src_vec_1.data());
+        }
     }
 
-    // allred_helper.hpp:84-96: run, read back print_core's result, validate.
+    // allred_helper.hpp:84-96: run, read print_core's result back into result_vec
+    // (num_els words), validate it (the printed report).  A failed run leaves
+    // result_vec as it was.
     int RunProgram(bool verbose = true) {
         if (status != ALLRED_OK) return status;
-        status = allred_run(&args, verbose ? 1 : 0, &report);
+        std::vector<uint32_t> res((std::size_t)num_els);
+        status = allred_run_io(&args, verbose ? 1 : 0, &report, nullptr, nullptr, res.data());
+        if (status == ALLRED_OK) result_vec.swap(res);
         return status;
     }
 };

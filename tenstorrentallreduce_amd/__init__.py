@@ -31,7 +31,7 @@ __all__ = [
     "dist_allreduce_host", "dist_allreduce_pipelined", "tree_broadcast_pipelined", "dist_workspace_bytes", "dist_program_stats", "Peer", "tune", "tuned", "last_launch",
     "ACC_FP32",
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
-    "MULTI_HIER", "MULTI_LOCAL",
+    "MULTI_HIER", "MULTI_LOCAL", "validate_device",
 ]
 
 
@@ -249,14 +249,44 @@ def parse_args(argv: Sequence[str], variant: int = BO) -> Args:
     return a
 
 
-def run(argv: Sequence[str], variant: int = BO, verbose: bool = False, exec_mode: int | None = None) -> Report:
-    """AllredConfig(argv) + RunProgram() in-process (allred_helper.hpp:47-97)."""
+def run(argv: Sequence[str], variant: int = BO, verbose: bool = False, exec_mode: int | None = None,
+        inputs: np.ndarray | None = None, outputs: bool = False):
+    """AllredConfig(argv) + RunProgram() in-process (allred_helper.hpp:47-97).
+    Returns the Report; with inputs (a (total, elems) uint16 array of arbitrary
+    rank vectors: validation skipped, mismatches -1) or outputs=True (every
+    rank's result wanted) it returns (Report, (total, elems) uint16 array or
+    None), as run_multi does (allred_run_io)."""
     a = parse_args(argv, variant)
     if exec_mode is not None:
         a.exec = exec_mode
     r = Report()
-    check(lib.allred_run(C.byref(a), int(verbose), C.byref(r)), "run")
-    return r
+    if inputs is None and not outputs:
+        check(lib.allred_run(C.byref(a), int(verbose), C.byref(r)), "run")
+        return r
+    n = a.num_tiles * 1024
+    out = np.zeros((a.total_nodes, n), dtype=np.uint16) if outputs else None
+    inp = None
+    if inputs is not None:
+        inp = np.ascontiguousarray(inputs, dtype=np.uint16)
+        if inp.shape != (a.total_nodes, n):
+            raise ValueError(f"inputs must be ({a.total_nodes}, {n})")
+    check(lib.allred_run_io(C.byref(a), int(verbose), C.byref(r), None if inp is None else inp.ctypes.data,
+                            None if out is None else out.ctypes.data, None), "run_io")
+    return r, out
+
+
+def validate_device(ranks_ptr: int, stride: int, n: int, rows: int, src0_ptr: int, src1_ptr: int, mult: float,
+                    error: float, round_mode: int = 0, stream=None) -> list:
+    """allred_validate_device: validate_result_vector on the GPU for `rows`
+    device-resident rows in one launch (k_validate).  Returns one dict per row:
+    bad (the host validator's count), first_bad (lowest bad element index, None
+    when the row has none), max_error (largest non-NaN |actual - expected| over
+    the bad elements, 0.0 when none)."""
+    rec = (_lib.RankCheck * max(rows, 1))()
+    check(lib.allred_validate_device(ranks_ptr, stride, n, rows, src0_ptr, src1_ptr, mult, error, round_mode, rec,
+                                     _stream_ptr(stream)), "validate_device")
+    return [{"bad": int(x.bad), "first_bad": None if x.first_bad == 2 ** 64 - 1 else int(x.first_bad),
+             "max_error": float(x.max_error)} for x in rec[:rows]]
 
 
 def run_cli(binary: str, args: Sequence[str], env: dict | None = None, timeout: float = 300):

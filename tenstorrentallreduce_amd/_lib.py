@@ -118,6 +118,10 @@ class LaunchInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class RankCheck(C.Structure):
+    _fields_ = [("bad", C.c_uint64), ("first_bad", C.c_uint64), ("max_error", C.c_float), ("reserved", C.c_int32)]
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -167,6 +171,9 @@ SIGNATURES = [
     ("allred_last_launch", C.c_int, [C.POINTER(LaunchInfo)]),
     ("allred_args_parse", C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Args)]),
     ("allred_run", C.c_int, [C.POINTER(Args), C.c_int, C.POINTER(Report)]),
+    ("allred_run_io", C.c_int, [C.POINTER(Args), C.c_int, C.POINTER(Report), _u16p, _u16p, _P]),
+    ("allred_validate_device", C.c_int,
+     [_u16p, C.c_uint64, C.c_size_t, C.c_int, _u16p, _u16p, C.c_float, C.c_float, C.c_int, C.POINTER(RankCheck), _P]),
     ("allred_comm_get_unique_id", C.c_int, [_P]),
     ("allred_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     ("allred_comm_init_all", C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_P)]),

@@ -8,7 +8,8 @@
 //   argv[9] or ALLRED_NODES   rank count (rectangular grids, e.g. 8 = 4x2)
 //   ALLRED_EXEC=fused         one-launch execution of the same arithmetic
 //   ALLRED_BF16_ROUND=rne     RNE bfloat16(float) for inputs/expected values
-//   ALLRED_CHECK_ALL=1        validate every rank, not only <printcore>
+//   ALLRED_CHECK_ALL=1        validate every rank, not only <printcore> (=device: the other
+//                             ranks on the GPU, where the result lives; same count)
 //   ALLRED_REPORT=1           print a JSON timing line to stderr
 //   ALLRED_STRICT=1           exit 1 on mismatch (the reference always exits 0)
 #include <cstdio>

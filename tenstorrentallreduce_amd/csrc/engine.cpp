@@ -899,6 +899,11 @@ int tsa::write_profile_log(const char* path, int N, int side, const uint64_t* st
 extern "C" {
 
 int allred_run(const allred_args* a, int verbose, allred_report* rep) {
+    return allred_run_io(a, verbose, rep, nullptr, nullptr, nullptr);
+}
+
+int allred_run_io(const allred_args* a, int verbose, allred_report* rep, const uint16_t* in_all, uint16_t* out_all,
+                  uint32_t* result_vec) {
     if (!a) return ALLRED_ERR_ARG;
     allred_report local_rep{};
     allred_report* R = rep ? rep : &local_rep;
@@ -913,7 +918,16 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
     if (print_core < 0 || print_core >= N) return ALLRED_ERR_ARG;
     R->bytes_per_rank = bytes;
     R->total_nodes = N;
-    if (a->gpus > 0) return run_multi_gpu(a, verbose, R);   // dist.cpp: one host thread per GPU
+    if (a->gpus > 0) {   // multi.cpp: one host thread per GPU
+        if (!result_vec) return run_multi_gpu(a, verbose, R, in_all, out_all);
+        // print_core's row out of every rank's result
+        std::vector<uint16_t> all;
+        if (!out_all) all.resize((size_t)N * n);
+        uint16_t* o = out_all ? out_all : all.data();
+        const int mst = run_multi_gpu(a, verbose, R, in_all, o);
+        if (mst == ALLRED_OK) std::memcpy(result_vec, o + (size_t)print_core * n, bytes);
+        return mst;
+    }
     DeviceGuard guard(a->device);
     if (!guard.ok) return ALLRED_ERR_HIP;
 
@@ -935,6 +949,9 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
     uint16_t *h_in = nullptr, *h_out = nullptr, *d_ranks = nullptr, *d_scratch = nullptr, *d_stage = nullptr;
     uint64_t* d_stamps = nullptr;
     void* d_ws = nullptr;
+    uint16_t* d_src = nullptr;      // ALLRED_CHECK_ALL=device: src0 | src1 on the device
+    const uint16_t* d_result = nullptr;   // where the timed run left every rank's result (device pointer)
+    size_t d_result_stride = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
     hipStream_t s = nullptr;
     const size_t all_bytes = (size_t)N * bytes;
@@ -952,8 +969,8 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
     const char* e2e_mode = std::getenv("ALLRED_E2E");
     const bool zero_copy = e2e_mode ? std::strcmp(e2e_mode, "zerocopy") == 0
                                     : (variant == ALLRED_BO && a->exec == ALLRED_EXEC_FUSED && N >= 8);
-    // "dma" over column chunks: the fused BO pass reduces every column with the same tree
-    // (tree_order[0]), so a column chunk of every rank is an allreduce of its own —
+    // "dma" over column chunks: the fused BO pass reduces a column on its own (block b's columns
+    // with the tree of rank b), so a column chunk of every rank is an allreduce of its own —
     // H2D(c + 1) | pass(c) | D2H(c - 1) on three streams, each copy a 2D DMA straight into /
     // out of the skewed device layout (no staging pass); same bits as the whole-bucket pass.
     // ALLRED_E2E_CHUNKS=c equal chunks (1 = one copy each way around one pass); unset: 8, where the
@@ -968,8 +985,12 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
         if (n % k == 0 && (n / k) % col_unit == 0) csz.assign(k, n / k);
     }
     const int chunks = (int)csz.size();
+    // The pass gives block b the tree of rank b, and a chunk's plan cuts its blocks anew: the bits
+    // of the whole-bucket pass only where every block's tree coincides (lo_rank_uniform).  The
+    // reference's inputs are checked within ERROR either way; the caller's own data (in_all) must
+    // come back as the plan leaves it, so there the other schedules go as one copy each way
     bool chunked = !zero_copy && chunks > 1 && variant == ALLRED_BO && a->exec == ALLRED_EXEC_FUSED &&
-                         !profile_log;
+                         !profile_log && (!in_all || lo_rank_uniform(plan->sched, N));
     std::vector<std::pair<size_t, allred_plan*>> cplans;   // one plan per distinct chunk size
     auto chunk_plan = [&](size_t len) -> allred_plan* {
         for (auto& cp : cplans)
@@ -989,9 +1010,12 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
     HIPCK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     HIPCK(hipHostMalloc((void**)&h_in, all_bytes, hipHostMallocDefault));
     HIPCK(hipHostMalloc((void**)&h_out, all_bytes, hipHostMallocDefault));
-    // even x loads src_1, odd x loads src_0 (allred_BO_2D.cpp:79-85)
-    for (int r = 0; r < N; ++r)
-        std::memcpy(h_in + (size_t)r * n, ((r % a->side_length) % 2 == 0) ? src1.data() : src0.data(), bytes);
+    if (in_all) {   // the caller's own rank vectors
+        std::memcpy(h_in, in_all, all_bytes);
+    } else {        // even x loads src_1, odd x loads src_0 (allred_BO_2D.cpp:79-85)
+        for (int r = 0; r < N; ++r)
+            std::memcpy(h_in + (size_t)r * n, ((r % a->side_length) % 2 == 0) ? src1.data() : src0.data(), bytes);
+    }
     HIPCK(hipMalloc((void**)&d_ranks, dev_bytes));
     HIPCK(hipMalloc((void**)&d_scratch, dev_bytes));
     HIPCK(hipMalloc((void**)&d_stage, all_bytes));
@@ -1096,6 +1120,8 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
         HIPCK(hipEventRecord(e3, s));
         HIPCK(hipStreamSynchronize(s));
         std::memcpy(h_out, h_in, all_bytes);  // (untimed) the result, for validation below
+        d_result = h_dev;
+        d_result_stride = n;
     } else {
         // timed: H2D | allreduce | D2H.  The 64 host buckets are contiguous: one
         // DMA each way (per-bucket copies pay ~70 us each), then one HBM pass
@@ -1110,6 +1136,10 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
         HIPCK(hipMemcpyAsync(h_out, d_stage, all_bytes, hipMemcpyDeviceToHost, s));
         HIPCK(hipEventRecord(e3, s));
         HIPCK(hipStreamSynchronize(s));
+    }
+    if (!d_result) {   // the DMA modes: the skewed device rows
+        d_result = d_ranks;
+        d_result_stride = stride;
     }
     if (!chunked) {
         HIPCK(hipEventElapsedTime(&ms, e1, e2));
@@ -1126,13 +1156,26 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
         }   // else: one device interval (hipEvents) for every rank, ticks from 0
         ST(write_profile_log(profile_log, N, a->side_length, zs.data(), ze.data()));
     }
-    {
+    if (!in_all) {   // arbitrary data has no closed-form check: the caller compares
         float maxe = 0;
         const uint32_t* res = reinterpret_cast<const uint32_t*>(h_out + (size_t)print_core * n);
         R->mismatches = allred_validate_result_vector(res, src0.data(), src1.data(), bytes / 4, (float)a->error,
                                                       (uint32_t)N, verbose, &maxe);
         R->max_error = maxe;
-        if (std::getenv("ALLRED_CHECK_ALL")) {  // extension: the reference checks one core only
+        const char* check_all = std::getenv("ALLRED_CHECK_ALL");
+        if (check_all && std::strcmp(check_all, "device") == 0) {
+            // the other N - 1 ranks counted where the result lives (k_validate), not in N - 1 host passes
+            const char* mode = std::getenv("ALLRED_BF16_ROUND");   // as the host validator reads it
+            const int round_mode = (mode && std::strcmp(mode, "rne") == 0) ? 1 : 0;
+            std::vector<allred_rank_check> rec((size_t)N);
+            HIPCK(hipMalloc((void**)&d_src, 2 * bytes));
+            HIPCK(hipMemcpyAsync(d_src, src0.data(), bytes, hipMemcpyHostToDevice, s));
+            HIPCK(hipMemcpyAsync(d_src + n, src1.data(), bytes, hipMemcpyHostToDevice, s));
+            ST(allred_validate_device(d_result, d_result_stride, n, N, d_src, d_src + n, (float)(N / 2),
+                                      (float)a->error, round_mode, rec.data(), s));
+            for (int r = 0; r < N; ++r)
+                if (r != print_core) R->mismatches += (int64_t)rec[(size_t)r].bad;
+        } else if (check_all) {  // extension: the reference checks one core only
             for (int r = 0; r < N; ++r) {
                 if (r == print_core) continue;
                 R->mismatches += allred_validate_result_vector(
@@ -1141,6 +1184,8 @@ int allred_run(const allred_args* a, int verbose, allred_report* rep) {
             }
         }
     }
+    if (out_all) std::memcpy(out_all, h_out, all_bytes);
+    if (result_vec) std::memcpy(result_vec, h_out + (size_t)print_core * n, bytes);
 done:
     if (sh) (void)hipStreamSynchronize(sh);
     if (sd) (void)hipStreamSynchronize(sd);
@@ -1157,6 +1202,7 @@ done:
     if (e3) (void)hipEventDestroy(e3);
     if (d_ws) (void)hipFree(d_ws);
     if (d_stamps) (void)hipFree(d_stamps);
+    if (d_src) (void)hipFree(d_src);
     if (d_ranks) (void)hipFree(d_ranks);
     if (d_scratch) (void)hipFree(d_scratch);
     if (d_stage) (void)hipFree(d_stage);
@@ -1164,6 +1210,41 @@ done:
     if (h_out) (void)hipHostFree(h_out);
     if (s) (void)hipStreamDestroy(s);
     allred_plan_destroy(plan);
+    return st;
+}
+
+int allred_validate_device(const uint16_t* ranks, uint64_t rank_stride, size_t n, int rows, const uint16_t* src0,
+                           const uint16_t* src1, float mult, float error, int round_mode, allred_rank_check* out,
+                           void* stream) {
+    // everything checkable without a GPU first (no HIP call before the arguments hold)
+    if (!ranks || !src0 || !src1 || !out || n == 0 || n % 8 || rows < 1 || rows > ALLRED_MAX_NODES ||
+        rank_stride < n || rank_stride % 8 || ((uintptr_t)ranks | (uintptr_t)src0 | (uintptr_t)src1) % 16)
+        return ALLRED_ERR_ARG;
+    // the launch's counters: one small allocation per (thread, device), kept
+    thread_local std::map<int, ValidateCounters*> counters;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ALLRED_ERR_HIP;
+    ValidateCounters*& d_ctr = counters[dev];
+    if (!d_ctr && hipMalloc((void**)&d_ctr, sizeof(ValidateCounters)) != hipSuccess) {
+        d_ctr = nullptr;
+        return ALLRED_ERR_NOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int st = ALLRED_OK;
+    ValidateCounters h;
+    // bad = 0, max_error = 0, first_bad = UINT64_MAX, in stream order before every launch
+    HIPCK(hipMemsetAsync(d_ctr, 0, offsetof(ValidateCounters, first_bad), s));
+    HIPCK(hipMemsetAsync(d_ctr->first_bad, 0xFF, sizeof(d_ctr->first_bad), s));
+    ST(launch_validate(ranks, rank_stride, n, rows, src0, src1, mult, error, round_mode != 0, d_ctr, s));
+    HIPCK(hipMemcpyAsync(&h, d_ctr, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    for (int r = 0; r < rows; ++r) {
+        out[r].bad = h.bad[r];
+        out[r].first_bad = h.first_bad[r];
+        std::memcpy(&out[r].max_error, &h.max_error_bits[r], sizeof(float));
+        out[r].reserved = 0;
+    }
+done:
     return st;
 }
 

@@ -82,6 +82,16 @@ int launch_lo_step(const uint16_t* src, uint64_t src_stride, uint16_t* dst, uint
                    int total, const int16_t* d_partner, size_t n, void* stream);
 int launch_copy_ranks(const uint16_t* src, uint64_t src_stride, uint16_t* dst, uint64_t dst_stride,
                       int total, size_t n, void* stream);
+// k_validate (allred_validate_device): `rows` <= ALLRED_MAX_NODES rows against bf16((src0 + src1) * mult) in
+// one launch.  d_ctr: the per-row device counters, zero except first_bad = ~0 before the launch (two 1D memsets:
+// the zero fields come first); max_error as the bit pattern of the non-negative float, so atomicMax orders it
+struct ValidateCounters {
+    uint64_t bad[ALLRED_MAX_NODES];
+    uint32_t max_error_bits[ALLRED_MAX_NODES];
+    uint64_t first_bad[ALLRED_MAX_NODES];
+};
+int launch_validate(const uint16_t* ranks, uint64_t stride, size_t n, int rows, const uint16_t* src0,
+                    const uint16_t* src1, float mult, float error, bool rne, ValidateCounters* d_ctr, void* stream);
 // mem_2D; acc16: the reference's bf16 accumulation (every add rounded), else fp32 rounded once
 int launch_mem_reduce(const uint16_t* ranks, uint64_t stride, size_t n, int total, uint16_t* dst, bool acc16,
                       void* stream);
@@ -92,7 +102,8 @@ int launch_rows_sum(const uint16_t* rows, uint64_t stride, size_t n, int nrows, 
                     void* stream);
 // allred_run with args->gpus > 0 (multi.cpp): the plan over G GPUs, one host thread each,
 // on the backend ALLRED_TRANSPORT / ALLRED_SHARE_GPU select
-int run_multi_gpu(const allred_args* a, int verbose, allred_report* report);
+int run_multi_gpu(const allred_args* a, int verbose, allred_report* report, const uint16_t* in_all = nullptr,
+                  uint16_t* out_all = nullptr);
 // run_multi_gpu: a flag every RCCL wait of `c` polls (another GPU's thread failed -> abort)
 void comm_set_cancel(allred_comm* c, const std::atomic<int>* cancel);
 // the checks allred_dist_allreduce applies to a desc (and its schedule)

@@ -1418,6 +1418,107 @@ __global__ __launch_bounds__(kBlock) void k_copy_ranks(const uint16_t* __restric
 }
 
 // ---------------------------------------------------------------------------
+// validate_result_vector (allred_helper.cpp:18-120, host_data.cpp) for `rows` device-resident
+// rows in one launch (allred_validate_device).  A workgroup owns tiles of kValCols 16-byte
+// columns for ALL rows: wave 0 loads the tile's src0 / src1 and leaves expected =
+// bf16((a + b) * mult) in LDS once per column, then wave w reads rows w, w + 4, ... of the tile
+// (1 KiB contiguous per wave-load, nontemporal, kValAhead loads in flight per lane), so the
+// traffic is rows * n * 2 + 2 * n * 2 bytes.  A lane touches the per-row LDS counters only
+// when its vector holds a bad element (the rare path of a correct run); a workgroup flushes
+// the rows it found bad once, at its end: the count by atomicAdd, the lowest index by
+// atomicMin, the largest diff by atomicMax on the bits of the non-negative float.  No
+// workgroup waits for another; every loop is bounded by the tile count and `rows`; nothing is
+// read past column n_vec of a row.
+// ---------------------------------------------------------------------------
+constexpr int kValCols = 64;   // 16-byte columns per tile: one column per lane
+constexpr int kValAhead = 8;   // row loads in flight per lane
+
+// float -> bfloat16 -> float exactly as host_data.cpp to_bf16 (truncating, or bf16_from_float_rne)
+__device__ __forceinline__ float val_bf16(float f, bool rne) {
+    const uint32_t u = __float_as_uint(f);
+    uint32_t h = u >> 16;
+    if (rne) h = (u & 0x7fffffffu) > 0x7f800000u ? (h | 0x40u) : (u + 0x7fffu + (h & 1u)) >> 16;
+    return __uint_as_float(h << 16);
+}
+
+__global__ __launch_bounds__(kBlock) void k_validate(const uint16_t* __restrict__ ranks, uint64_t stride,
+                                                     uint64_t n_vec, int rows, const uint4* __restrict__ src0,
+                                                     const uint4* __restrict__ src1, float mult, float error,
+                                                     bool rne, ValidateCounters* __restrict__ ctr) {
+    __shared__ float s_exp[8][kValCols];
+    __shared__ unsigned long long s_bad[ALLRED_MAX_NODES], s_first[ALLRED_MAX_NODES];
+    __shared__ unsigned int s_max[ALLRED_MAX_NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x < ALLRED_MAX_NODES) {
+        s_bad[threadIdx.x] = 0;
+        s_first[threadIdx.x] = ~0ull;
+        s_max[threadIdx.x] = 0;
+    }
+    const uint64_t tiles = (n_vec + kValCols - 1) / kValCols;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // the same trip count in every wave
+        const uint64_t v = t * kValCols + lane;
+        const bool ok = v < n_vec;   // the last tile may be ragged
+        if (w == 0 && ok) {
+            const uint4 a = src0[v], b = src1[v];
+            const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s_exp[2 * k][lane] = val_bf16((lo_f(aw[k]) + lo_f(bw[k])) * mult, rne);
+                s_exp[2 * k + 1][lane] = val_bf16((hi_f(aw[k]) + hi_f(bw[k])) * mult, rne);
+            }
+        }
+        __syncthreads();   // expected (and, the first time, the zeroed counters) visible
+        float e[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = s_exp[j][lane];
+        for (int r0 = w; r0 < rows; r0 += 4 * kValAhead) {
+            uint4 x[kValAhead];
+#pragma unroll
+            for (int u = 0; u < kValAhead; ++u) {
+                const int r = r0 + 4 * u;
+                x[u] = (ok && r < rows) ? ld_nt(reinterpret_cast<const uint4*>(ranks + (uint64_t)r * stride) + v)
+                                        : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+            for (int u = 0; u < kValAhead; ++u) {
+                const int r = r0 + 4 * u;
+                if (!ok || r >= rows) continue;
+                const uint32_t xw[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+                float d[8];
+                bool any = false;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    d[2 * k] = fabsf(lo_f(xw[k]) - e[2 * k]);
+                    d[2 * k + 1] = fabsf(hi_f(xw[k]) - e[2 * k + 1]);
+                    any = any || !(d[2 * k] <= error) || !(d[2 * k + 1] <= error);   // NaN is bad
+                }
+                if (any) {
+                    unsigned int count = 0, first = 8, maxb = 0;
+#pragma unroll
+                    for (int j = 7; j >= 0; --j) {
+                        if (d[j] <= error) continue;
+                        ++count;
+                        first = (unsigned)j;
+                        const unsigned int bits = __float_as_uint(d[j]);   // d >= 0 or NaN
+                        if (d[j] == d[j] && bits > maxb) maxb = bits;
+                    }
+                    atomicAdd(&s_bad[r], (unsigned long long)count);
+                    atomicMin(&s_first[r], (unsigned long long)(v * 8 + first));
+                    atomicMax(&s_max[r], maxb);
+                }
+            }
+        }
+        __syncthreads();   // every wave has read s_exp before the next tile's overwrite
+    }
+    // (the loop ends with a barrier, and every workgroup runs at least one tile: grid <= tiles)
+    if ((int)threadIdx.x < rows && s_bad[threadIdx.x]) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(&ctr->bad[threadIdx.x]), s_bad[threadIdx.x]);
+        atomicMin(reinterpret_cast<unsigned long long*>(&ctr->first_bad[threadIdx.x]), s_first[threadIdx.x]);
+        atomicMax(&ctr->max_error_bits[threadIdx.x], s_max[threadIdx.x]);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 int last_error() { return hip_status((int)hipGetLastError()); }
@@ -1821,6 +1922,20 @@ int launch_copy_ranks(const uint16_t* src, uint64_t src_stride, uint16_t* dst, u
     const uint64_t nv = n / 8;
     hipLaunchKernelGGL(k_copy_ranks, dim3(grid_all(nv), total), dim3(kBlock), 0, (hipStream_t)stream, src, src_stride,
                        dst, dst_stride, nv);
+    return last_error();
+}
+
+int launch_validate(const uint16_t* ranks, uint64_t stride, size_t n, int rows, const uint16_t* src0,
+                    const uint16_t* src1, float mult, float error, bool rne, ValidateCounters* d_ctr, void* stream) {
+    if (n == 0 || n % 8 || stride % 8 || stride < n || rows < 1 || rows > ALLRED_MAX_NODES || !d_ctr ||
+        !aligned16(ranks) || !aligned16(src0) || !aligned16(src1))
+        return ALLRED_ERR_ARG;
+    const uint64_t nv = n / 8, tiles = (nv + kValCols - 1) / kValCols;
+    // one tile per workgroup up to kMaxGrid, then grid-stride (99 VGPRs, 3.3 KiB of LDS: 4 workgroups per CU)
+    const unsigned grid = (unsigned)(tiles < (uint64_t)kMaxGrid ? tiles : (uint64_t)kMaxGrid);
+    hipLaunchKernelGGL(k_validate, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, ranks, stride, nv, rows,
+                       reinterpret_cast<const uint4*>(src0), reinterpret_cast<const uint4*>(src1), mult, error, rne,
+                       d_ctr);
     return last_error();
 }
 

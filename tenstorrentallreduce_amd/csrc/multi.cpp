@@ -671,11 +671,12 @@ int allred_run_multi(const allred_args* a, const allred_multi_opts* o, int verbo
 }  // extern "C"
 
 // allred_run with args->gpus > 0: the backend from the environment
-int tsa::run_multi_gpu(const allred_args* a, int verbose, allred_report* R) {
+int tsa::run_multi_gpu(const allred_args* a, int verbose, allred_report* R, const uint16_t* in_all,
+                       uint16_t* out_all) {
     allred_multi_opts o{};
     if (env_transport(&o.transport) != ALLRED_OK) return ALLRED_ERR_ARG;
     const char* share = std::getenv("ALLRED_SHARE_GPU");
     o.share_device = share && *share && std::strcmp(share, "0") != 0;
     if (const char* t = std::getenv("ALLRED_RCCL_TIMEOUT_MS")) o.timeout_ms = std::max(0, std::atoi(t));
-    return allred_run_multi(a, &o, verbose, R, nullptr, nullptr);
+    return allred_run_multi(a, &o, verbose, R, in_all, out_all);
 }
