@@ -29,7 +29,10 @@ extern "C" {
  * allred_last_launch is new.  ABI 6 (round 5): the hierarchical forms' hand-off area holds
  * 6 data bytes + a 16-bit epoch per word — peers of different ABIs must not connect.
  * Still ABI 7: allred_run_io, allred_validate_device and allred_rank_check are additions —
- * no existing struct layout, signature or behaviour changes, so the version stays. */
+ * no existing struct layout, signature or behaviour changes, so the version stays.
+ * Still ABI 7: allred_plan_reduce_scatter / allred_plan_all_gather and allred_dist_reduce_scatter /
+ * allred_dist_all_gather (+ their _host twins) are additions too — the two halves of the BO
+ * allreduce as calls of their own, on the existing plans, descs and communicators. */
 #define ALLRED_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------- */
@@ -231,6 +234,42 @@ size_t allred_plan_workspace_bytes(const allred_plan* plan);
 /* workspace: device memory of allred_plan_workspace_bytes() (may be NULL when 0) */
 int allred_plan_execute(allred_plan* plan, uint16_t* ranks, uint64_t rank_stride,
                         void* workspace, void* stream);
+/* The two halves of the BO allreduce as collectives of their own (sharded training:
+ * (P + 1) n bytes of HBM traffic each, where the allreduce moves 2 P n).  Both take a plan
+ * whose variant is ALLRED_BO (any BO grid, 2D or 1D algo; LO / MEM plans:
+ * ALLRED_ERR_UNSUPPORTED); workspace may be NULL (BO plans have none).  blk =
+ * elems_per_rank / total.  The argument checks are allred_plan_execute's (stride < n, stride
+ * % 8, ranks not 16-byte aligned: ALLRED_ERR_ARG), made before anything is launched.  A plan
+ * with total == 1 is a no-op (out of place: a copy of the one block).
+ *
+ * allred_plan_reduce_scatter — the RS loop of allred_BO_2D/kernels/dataflow_kernel.cpp:152-213
+ * (+ compute_kernel.cpp:35-67).  In place (out == NULL): block b of rank b's row receives the
+ * value the BO allreduce gives block b: tree b of the schedule (tree_order[b]), every add
+ * rounded to bf16 — the bits allred_plan_execute leaves there.
+ *   ALLRED_EXEC_FUSED plan: one HBM pass (k_rs_reg / k_rs_lds / k_rs_pipe) that writes nothing
+ *     else: every other element of every row, and everything past element n of a row, keeps
+ *     its bits.
+ *   ALLRED_EXEC_STEPS plan: the reference's reduce-scatter loop alone, one launch per step
+ *     k = 0 .. S-1 (whatever the tune key steps_form says).  The blocks a rank does not own
+ *     are left holding the reference's partial sums: UNSPECIFIED.  Nothing past element n of
+ *     a row is touched.
+ * Out of place (out != NULL, fused plans only; a steps-form plan: ALLRED_ERR_UNSUPPORTED):
+ * rank b's reduced block goes to out + b * out_stride (blk elements) and `ranks` is only read.
+ * ALLRED_ERR_ARG: out_stride < blk, out_stride % 8 != 0, out not 16-byte aligned, or
+ * [out, out + total * out_stride) overlapping [ranks, ranks + total * rank_stride).
+ *
+ * allred_plan_all_gather — the AG loop of allred_BO_2D/kernels/dataflow_kernel.cpp:219-267.
+ * In place (in == NULL): block b of rank b is copied — all 16 bits, NaN payloads included — to
+ * block b of every rank (fused: one pass, k_ag; steps form: one launch per step k = S-1 .. 0).
+ * Out of place (fused plans only): rank b's block is read from in + b * in_stride instead and
+ * written to every rank, b included; `in` is only read; the alignment, stride and overlap
+ * rules are those of `out`.  Nothing but the n elements of each row is written.
+ * reduce_scatter then all_gather on one bucket = allred_plan_execute, bit for bit, in any
+ * mix of fused and steps-form plans of the same schedule. */
+int allred_plan_reduce_scatter(allred_plan* plan, uint16_t* ranks, uint64_t rank_stride, uint16_t* out,
+                               uint64_t out_stride, void* workspace, void* stream);
+int allred_plan_all_gather(allred_plan* plan, uint16_t* ranks, uint64_t rank_stride, const uint16_t* in,
+                           uint64_t in_stride, void* workspace, void* stream);
 /* number of kernel launches one execute enqueues (for per-launch accounting) */
 int allred_plan_launches(const allred_plan* plan);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
@@ -496,6 +535,27 @@ typedef int (*allred_exchange_fn)(void* ctx, int peer, int nsend, const allred_s
                                   int nrecv, const allred_seg* recv);
 int allred_dist_allreduce_host(const allred_dist_desc* desc, int rank, uint16_t* buf,
                                uint16_t* scratch, allred_exchange_fn exchange, void* ctx);
+
+/* The halves of the per-rank BO program as calls of their own: the program is S
+ * reduce-scatter steps (allred_BO_2D/kernels/dataflow_kernel.cpp:152-213) followed by S
+ * all-gather steps (:219-267); these run the first S, or the last S, steps of the SAME cached
+ * program (same segments, adds, bounded waits; check mode verifies the steps that run and
+ * poisons their receive regions).  After reduce_scatter rank r's block r (elems / total
+ * elements at r * elems / total) is final — the BO allreduce's bits — and its other blocks are
+ * UNSPECIFIED (the reference's partial sums); after all_gather every rank holds every owner's
+ * block, copied bit for bit.  reduce_scatter then all_gather = allred_dist_allreduce with
+ * channels = 1.  ALLRED_ERR_UNSUPPORTED (before any exchange): a variant other than
+ * ALLRED_BO, local_ranks > 1, channels > 1 (0 and 1 both mean the plain schedule here: with
+ * link-spreading channels the block a rank owns differs per channel).  workspace:
+ * allred_dist_workspace_bytes(desc); scratch: elems elements. */
+int allred_dist_reduce_scatter(allred_comm* comm, const allred_dist_desc* desc, uint16_t* buf, void* workspace,
+                               void* stream);
+int allred_dist_all_gather(allred_comm* comm, const allred_dist_desc* desc, uint16_t* buf, void* workspace,
+                           void* stream);
+int allred_dist_reduce_scatter_host(const allred_dist_desc* desc, int rank, uint16_t* buf, uint16_t* scratch,
+                                    allred_exchange_fn exchange, void* ctx);
+int allred_dist_all_gather_host(const allred_dist_desc* desc, int rank, uint16_t* buf, uint16_t* scratch,
+                                allred_exchange_fn exchange, void* ctx);
 
 /* ---- bounded RCCL (a bad configuration returns an error
  * instead of hanging; the reference hangs, allred_helper.hpp:84-96) -------

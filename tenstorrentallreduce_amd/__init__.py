@@ -31,7 +31,8 @@ __all__ = [
     "dist_allreduce_host", "dist_allreduce_pipelined", "tree_broadcast_pipelined", "dist_workspace_bytes", "dist_program_stats", "Peer", "tune", "tuned", "last_launch",
     "ACC_FP32",
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
-    "MULTI_HIER", "MULTI_LOCAL", "validate_device",
+    "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
+    "dist_reduce_scatter_host", "dist_all_gather_host",
 ]
 
 
@@ -220,6 +221,20 @@ class Plan:
         """stamps_ptr: device memory of stamp_words uint64 (schedule form only)."""
         check(lib.allred_plan_execute_profiled(self._h, ranks_ptr, stride, workspace_ptr, stamps_ptr,
                                                _stream_ptr(stream)), "plan_execute")
+
+    def reduce_scatter(self, ranks_ptr: int, stride: int, out_ptr: int | None = None, out_stride: int = 0,
+                       workspace_ptr: int | None = None, stream=None) -> None:
+        """allred_plan_reduce_scatter (BO plans): block b of the allreduce to rank b's
+        row, or — fused plans — to out_ptr + b * out_stride elements, ranks only read."""
+        check(lib.allred_plan_reduce_scatter(self._h, ranks_ptr, stride, out_ptr or None, out_stride, workspace_ptr,
+                                             _stream_ptr(stream)), "plan_reduce_scatter")
+
+    def all_gather(self, ranks_ptr: int, stride: int, in_ptr: int | None = None, in_stride: int = 0,
+                   workspace_ptr: int | None = None, stream=None) -> None:
+        """allred_plan_all_gather (BO plans): block b of rank b — or, fused plans, of
+        in_ptr + b * in_stride elements — copied bit for bit to block b of every rank."""
+        check(lib.allred_plan_all_gather(self._h, ranks_ptr, stride, in_ptr or None, in_stride, workspace_ptr,
+                                         _stream_ptr(stream)), "plan_all_gather")
 
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
@@ -415,11 +430,39 @@ def tree_broadcast_pipelined(cur_ptr: int, prev_ptr: int, stride: int, n: int, a
                                               prev_src_ptr, _stream_ptr(stream)), "tree_broadcast_pipelined")
 
 
+def dist_reduce_scatter(comm: Comm, desc: DistDesc, buf_ptr: int, workspace_ptr: int, stream=None) -> None:
+    """The reduce-scatter half of dist_allreduce's BO program (allred_dist_reduce_scatter):
+    rank r's block r final, its other blocks unspecified."""
+    check(lib.allred_dist_reduce_scatter(comm._h, C.byref(desc), buf_ptr, workspace_ptr, _stream_ptr(stream)),
+          "dist_reduce_scatter")
+
+
+def dist_all_gather(comm: Comm, desc: DistDesc, buf_ptr: int, workspace_ptr: int, stream=None) -> None:
+    """The all-gather half (allred_dist_all_gather): every rank gets every owner's block."""
+    check(lib.allred_dist_all_gather(comm._h, C.byref(desc), buf_ptr, workspace_ptr, _stream_ptr(stream)),
+          "dist_all_gather")
+
+
 def dist_allreduce_host(desc: DistDesc, rank: int, buf: np.ndarray, scratch: np.ndarray,
                         exchange: Callable[[int, list, list], None]) -> None:
     """Host-memory twin: `exchange(peer, sends, recvs)` gets lists of writable
     uint8 numpy views and must send every send view / fill every recv view."""
+    _dist_host(lib.allred_dist_allreduce_host, "dist_allreduce_host", desc, rank, buf, scratch, exchange)
 
+
+def dist_reduce_scatter_host(desc: DistDesc, rank: int, buf: np.ndarray, scratch: np.ndarray,
+                             exchange: Callable[[int, list, list], None]) -> None:
+    """Host-memory twin of dist_reduce_scatter (exchange as dist_allreduce_host's)."""
+    _dist_host(lib.allred_dist_reduce_scatter_host, "dist_reduce_scatter_host", desc, rank, buf, scratch, exchange)
+
+
+def dist_all_gather_host(desc: DistDesc, rank: int, buf: np.ndarray, scratch: np.ndarray,
+                         exchange: Callable[[int, list, list], None]) -> None:
+    """Host-memory twin of dist_all_gather (exchange as dist_allreduce_host's)."""
+    _dist_host(lib.allred_dist_all_gather_host, "dist_all_gather_host", desc, rank, buf, scratch, exchange)
+
+
+def _dist_host(fn, what: str, desc: DistDesc, rank: int, buf: np.ndarray, scratch: np.ndarray, exchange) -> None:
     def _cb(_ctx, peer, nsend, send, nrecv, recv):
         try:
             def views(segs, n):
@@ -437,8 +480,7 @@ def dist_allreduce_host(desc: DistDesc, rank: int, buf: np.ndarray, scratch: np.
 
     cb = _lib.EXCHANGE_FN(_cb)
     assert buf.dtype == np.uint16 and scratch.dtype == np.uint16
-    check(lib.allred_dist_allreduce_host(C.byref(desc), rank, buf.ctypes.data, scratch.ctypes.data, cb, None),
-          "dist_allreduce_host")
+    check(fn(C.byref(desc), rank, buf.ctypes.data, scratch.ctypes.data, cb, None), what)
 
 
 PEER_TIMEOUT, PEER_WIN_CACHED, PEER_FLAGS_CACHED = _lib.PEER_TIMEOUT, _lib.PEER_WIN_CACHED, _lib.PEER_FLAGS_CACHED

@@ -162,6 +162,8 @@ SIGNATURES = [
     ("allred_plan_destroy", C.c_int, [_P]),
     ("allred_plan_workspace_bytes", C.c_size_t, [_P]),
     ("allred_plan_execute", C.c_int, [_P, _u16p, C.c_uint64, _P, _P]),
+    ("allred_plan_reduce_scatter", C.c_int, [_P, _u16p, C.c_uint64, _u16p, C.c_uint64, _P, _P]),
+    ("allred_plan_all_gather", C.c_int, [_P, _u16p, C.c_uint64, _u16p, C.c_uint64, _P, _P]),
     ("allred_plan_launches", C.c_int, [_P]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
@@ -186,6 +188,10 @@ SIGNATURES = [
     ("allred_dist_program_stats", C.c_int,
      [C.POINTER(DistDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("allred_dist_allreduce_host", C.c_int, [C.POINTER(DistDesc), C.c_int, _u16p, _u16p, EXCHANGE_FN, _P]),
+    ("allred_dist_reduce_scatter", C.c_int, [_P, C.POINTER(DistDesc), _u16p, _P, _P]),
+    ("allred_dist_all_gather", C.c_int, [_P, C.POINTER(DistDesc), _u16p, _P, _P]),
+    ("allred_dist_reduce_scatter_host", C.c_int, [C.POINTER(DistDesc), C.c_int, _u16p, _u16p, EXCHANGE_FN, _P]),
+    ("allred_dist_all_gather_host", C.c_int, [C.POINTER(DistDesc), C.c_int, _u16p, _u16p, EXCHANGE_FN, _P]),
     ("allred_comm_set_timeout", C.c_int, [_P, C.c_int]),
     ("allred_comm_wait", C.c_int, [_P, _P]),
     ("allred_comm_aborted", C.c_int, [_P]),

@@ -258,20 +258,36 @@ int add_launches(const Step& st) { return ((int)st.add_off.size() + kMaxAddSegs 
 // bf16 quiet NaN) before its step, so an element the transport never delivered
 // cannot pass as data — it turns the result into NaN instead of stale bytes.
 constexpr uint16_t kPoison = 0xFFFF;
-std::mutex g_verified_mu;
-std::map<ProgKey, int> g_verified;
 
-int verify_program(const allred_dist_desc* d, const allred_schedule& s, int rank, int C) {
+// The part of a rank's cached program a call runs: all of it (the allreduce), or one half of
+// the BO program — its first S steps are the reduce-scatter, its last S the all-gather
+// (allred_dist_reduce_scatter / allred_dist_all_gather run a slice of the same vector).
+enum Part { kWhole = 0, kReduceScatter = 1, kAllGather = 2 };
+void part_range(Part part, size_t steps, size_t* first, size_t* last) {
+    *first = part == kAllGather ? steps / 2 : 0;
+    *last = part == kReduceScatter ? steps / 2 : steps;
+}
+
+// the verdicts of a (desc, rank), one per part (0: not verified yet, else status + 1)
+struct Verdicts {
+    int st1[3] = {0, 0, 0};
+};
+std::mutex g_verified_mu;
+std::map<ProgKey, Verdicts> g_verified;
+
+int verify_program(const allred_dist_desc* d, const allred_schedule& s, int rank, int C, Part part = kWhole) {
     const ProgKey key{d->algo, d->variant, d->side_length, d->total_nodes, d->elems, C, rank};
     {
         std::lock_guard<std::mutex> g(g_verified_mu);
         const auto it = g_verified.find(key);
-        if (it != g_verified.end()) return it->second;
+        if (it != g_verified.end() && it->second.st1[part]) return it->second.st1[part] - 1;
     }
     const size_t n = (size_t)d->elems;
     const auto mine = cached_program(d, s, rank, C);
     int st = ALLRED_OK;
-    for (size_t k = 0; k < mine->size() && st == ALLRED_OK; ++k) {
+    size_t first, last;
+    part_range(part, mine->size(), &first, &last);
+    for (size_t k = first; k < last && st == ALLRED_OK; ++k) {   // only the steps that run
         const Step& step = (*mine)[k];
         std::vector<Seg> all;
         for (size_t x = 0; x < step.ex.size() && st == ALLRED_OK; ++x) {
@@ -298,7 +314,7 @@ int verify_program(const allred_dist_desc* d, const allred_schedule& s, int rank
     }
     std::lock_guard<std::mutex> g(g_verified_mu);
     if (g_verified.size() >= kMaxCachedPrograms) g_verified.clear();
-    g_verified[key] = st;
+    g_verified[key].st1[part] = st + 1;
     return st;
 }
 
@@ -380,7 +396,7 @@ void host_rows_sum(const uint16_t* rows, size_t stride, size_t n, int nrows, boo
 }
 
 int run_program(allred_comm* c, const allred_dist_desc* d, const allred_schedule& s, uint16_t* bucket,
-                uint16_t* staging, void* stream);
+                uint16_t* staging, void* stream, Part part = kWhole);
 
 // ---- bounded RCCL ----------------------------------------------------------
 // The reference's host blocks in Finish() forever when a core never signals
@@ -769,17 +785,21 @@ int allred_tree_broadcast_pipelined(uint16_t* cur, uint16_t* prev, uint64_t stri
 namespace {
 
 // the exchange steps of the rank's program on `bucket` (reduce-scatter adds staged in
-// `staging`), after the local tree; the caller broadcasts
+// `staging`), after the local tree; the caller broadcasts.  part: the whole program, or the
+// slice of the cached vector that is its reduce-scatter / all-gather half
 int run_program(allred_comm* c, const allred_dist_desc* d, const allred_schedule& s, uint16_t* bucket,
-                uint16_t* staging, void* stream) {
+                uint16_t* staging, void* stream, Part part) {
     hipStream_t hs = (hipStream_t)stream;
     const size_t n = (size_t)d->elems;
     int st = ALLRED_OK;
     const int C = channels_for(s, d->channels, n);
     const auto prog = cached_program(d, s, c->rank, C);
     const bool check = tune(Tune::check) != 0;
-    if (check && (st = verify_program(d, s, c->rank, C)) != ALLRED_OK) return st;
-    for (const Step& step : *prog) {
+    if (check && (st = verify_program(d, s, c->rank, C, part)) != ALLRED_OK) return st;
+    size_t first, last;
+    part_range(part, prog->size(), &first, &last);
+    for (size_t q = first; q < last; ++q) {
+        const Step& step = (*prog)[q];
         if (check)   // poison every receive region of the step (stream-ordered before the group)
             for (const Exch& e : step.ex)
                 for (const Seg& g : e.recv)
@@ -810,9 +830,99 @@ int run_program(allred_comm* c, const allred_dist_desc* d, const allred_schedule
     return ALLRED_OK;
 }
 
+// run_program's host twin: the same slice of the same cached program, exchanges by callback
+int run_program_host(const allred_dist_desc* d, const allred_schedule& s, int rank, uint16_t* bucket,
+                     uint16_t* scratch, allred_exchange_fn exchange, void* ctx, Part part) {
+    int st = ALLRED_OK;
+    const int C = channels_for(s, d->channels, (size_t)d->elems);
+    const auto prog = cached_program(d, s, rank, C);
+    const bool check = tune(Tune::check) != 0;
+    if (check && (st = verify_program(d, s, rank, C, part)) != ALLRED_OK) return st;
+    std::vector<allred_seg> snd, rcv;
+    size_t first, last;
+    part_range(part, prog->size(), &first, &last);
+    for (size_t q = first; q < last; ++q) {
+        const Step& step = (*prog)[q];
+        for (const Exch& e : step.ex) {  // channels in order: every channel is a perfect matching
+            snd.clear();
+            rcv.clear();
+            for (const Seg& g : e.send) snd.push_back(allred_seg{bucket + g.off, g.len * 2});
+            for (const Seg& g : e.recv) {
+                uint16_t* at = (e.recv_to_bucket ? bucket : scratch) + g.off;
+                if (check) std::fill(at, at + g.len, kPoison);
+                rcv.push_back(allred_seg{at, g.len * 2});
+            }
+            if (exchange(ctx, e.peer, (int)snd.size(), snd.data(), (int)rcv.size(), rcv.data()) != 0)
+                return ALLRED_ERR_TRANSPORT;
+        }
+        for (size_t i = 0; i < step.add_off.size(); ++i)   // the device path's one add launch per step
+            host_add(bucket + step.add_off[i], scratch + step.add_off[i], step.add_len[i]);
+    }
+    return ALLRED_OK;
+}
+
+// what the half-program entry points refuse (before any exchange): anything but a flat,
+// one-channel BO desc.  With link-spreading channels the block a rank owns differs per channel.
+int half_check_desc(const allred_dist_desc* d, allred_schedule* s) {
+    if (!d) return ALLRED_ERR_ARG;
+    if (d->variant != ALLRED_BO || d->local_ranks > 1 || d->channels > 1) return ALLRED_ERR_UNSUPPORTED;
+    return check_desc(d, s);
+}
+
+// channels 0 (auto) would spread a large bucket over the links: the halves run the plain schedule
+allred_dist_desc plain_desc(const allred_dist_desc* d) {
+    allred_dist_desc p = *d;
+    p.channels = 1;
+    p.local_ranks = 1;
+    return p;
+}
+
+int dist_half(allred_comm* c, const allred_dist_desc* d, uint16_t* buf, void* workspace, void* stream, Part part) {
+    if (!c || !buf || !workspace) return ALLRED_ERR_ARG;
+    if (c->aborted) return ALLRED_ERR_TRANSPORT;
+    if (c->pend) return ALLRED_ERR_ARG;   // a pipelined bucket's partial lives in the workspace
+    allred_schedule s;
+    int st = half_check_desc(d, &s);
+    if (st != ALLRED_OK) return st;
+    if (d->total_nodes != c->nranks) return ALLRED_ERR_ARG;
+    if (((uintptr_t)buf | (uintptr_t)workspace) % 16) return ALLRED_ERR_ARG;
+    const allred_dist_desc pd = plain_desc(d);
+    return run_program(c, &pd, s, buf, static_cast<uint16_t*>(workspace), stream, part);
+}
+
+int dist_half_host(const allred_dist_desc* d, int rank, uint16_t* buf, uint16_t* scratch, allred_exchange_fn exchange,
+                   void* ctx, Part part) {
+    if (!buf || !scratch || !exchange) return ALLRED_ERR_ARG;
+    allred_schedule s;
+    int st = half_check_desc(d, &s);
+    if (st != ALLRED_OK) return st;
+    if (rank < 0 || rank >= d->total_nodes) return ALLRED_ERR_ARG;
+    const allred_dist_desc pd = plain_desc(d);
+    return run_program_host(&pd, s, rank, buf, scratch, exchange, ctx, part);
+}
+
 }  // namespace
 
 extern "C" {
+
+int allred_dist_reduce_scatter(allred_comm* c, const allred_dist_desc* d, uint16_t* buf, void* workspace,
+                               void* stream) {
+    return dist_half(c, d, buf, workspace, stream, kReduceScatter);
+}
+
+int allred_dist_all_gather(allred_comm* c, const allred_dist_desc* d, uint16_t* buf, void* workspace, void* stream) {
+    return dist_half(c, d, buf, workspace, stream, kAllGather);
+}
+
+int allred_dist_reduce_scatter_host(const allred_dist_desc* d, int rank, uint16_t* buf, uint16_t* scratch,
+                                    allred_exchange_fn exchange, void* ctx) {
+    return dist_half_host(d, rank, buf, scratch, exchange, ctx, kReduceScatter);
+}
+
+int allred_dist_all_gather_host(const allred_dist_desc* d, int rank, uint16_t* buf, uint16_t* scratch,
+                                allred_exchange_fn exchange, void* ctx) {
+    return dist_half_host(d, rank, buf, scratch, exchange, ctx, kAllGather);
+}
 
 int allred_dist_program_stats(const allred_dist_desc* d, int rank, int* steps, int* launches, int* segments) {
     allred_schedule s;
@@ -873,27 +983,7 @@ int allred_dist_allreduce_host(const allred_dist_desc* d, int rank, uint16_t* bu
         bucket = scratch + n;
         host_tree_reduce(buf, n, n, ls, bucket);
     }
-    const int C = channels_for(s, d->channels, n);
-    const auto prog = cached_program(d, s, rank, C);
-    const bool check = tune(Tune::check) != 0;
-    if (check && (st = verify_program(d, s, rank, C)) != ALLRED_OK) return st;
-    std::vector<allred_seg> snd, rcv;
-    for (const Step& step : *prog) {
-        for (const Exch& e : step.ex) {  // channels in order: every channel is a perfect matching
-            snd.clear();
-            rcv.clear();
-            for (const Seg& g : e.send) snd.push_back(allred_seg{bucket + g.off, g.len * 2});
-            for (const Seg& g : e.recv) {
-                uint16_t* at = (e.recv_to_bucket ? bucket : scratch) + g.off;
-                if (check) std::fill(at, at + g.len, kPoison);
-                rcv.push_back(allred_seg{at, g.len * 2});
-            }
-            if (exchange(ctx, e.peer, (int)snd.size(), snd.data(), (int)rcv.size(), rcv.data()) != 0)
-                return ALLRED_ERR_TRANSPORT;
-        }
-        for (size_t i = 0; i < step.add_off.size(); ++i)   // the device path's one add launch per step
-            host_add(bucket + step.add_off[i], scratch + step.add_off[i], step.add_len[i]);
-    }
+    if ((st = run_program_host(d, s, rank, bucket, scratch, exchange, ctx, kWhole)) != ALLRED_OK) return st;
     if (d->local_ranks > 1)
         for (int r = 0; r < d->local_ranks; ++r) std::memcpy(buf + (size_t)r * n, bucket, n * 2);
     return ALLRED_OK;

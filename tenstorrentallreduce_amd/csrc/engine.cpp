@@ -779,6 +779,64 @@ int allred_plan_execute(allred_plan* p, uint16_t* ranks, uint64_t stride, void* 
     return allred_plan_execute_profiled(p, ranks, stride, workspace, nullptr, stream);
 }
 
+}  // extern "C"
+
+namespace {
+
+// The argument checks allred_plan_reduce_scatter / allred_plan_all_gather share, before any
+// HIP call: execute's own, then those of the side buffer (`out` / `in`: `total` rows of blk
+// elements, side_stride apart), which only fused plans take.
+int rs_ag_check(const allred_plan* p, const uint16_t* ranks, uint64_t stride, const uint16_t* side,
+                uint64_t side_stride) {
+    if (!p || !ranks) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO) return ALLRED_ERR_UNSUPPORTED;
+    if (stride < p->n || stride % 8 || (uintptr_t)ranks % 16) return ALLRED_ERR_ARG;
+    if (!side) return ALLRED_OK;
+    if (p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (side_stride < p->block_elems || side_stride % 8 || (uintptr_t)side % 16) return ALLRED_ERR_ARG;
+    const uintptr_t a0 = (uintptr_t)ranks, a1 = a0 + 2 * (uintptr_t)p->total * stride;
+    const uintptr_t b0 = (uintptr_t)side, b1 = b0 + 2 * (uintptr_t)p->total * side_stride;
+    return a0 < b1 && b0 < a1 ? ALLRED_ERR_ARG : ALLRED_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int allred_plan_reduce_scatter(allred_plan* p, uint16_t* ranks, uint64_t stride, uint16_t* out, uint64_t out_stride,
+                               void* workspace, void* stream) {
+    (void)workspace;   // BO plans have none
+    int st = rs_ag_check(p, ranks, stride, out, out_stride);
+    if (st != ALLRED_OK) return st;
+    const int N = p->total, steps = p->sched.steps;
+    if (N == 1 && !out) return ALLRED_OK;   // one rank owns its one block already
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    if (p->desc.exec == ALLRED_EXEC_FUSED)
+        return launch_reduce_scatter(ranks, stride, p->n, N, p->d_order, out, out_stride, stream);
+    // the reference's reduce-scatter loop alone, one launch per step (whatever steps_form says)
+    for (int k = 0; k < steps && st == ALLRED_OK; ++k)
+        st = launch_rs_step(ranks, stride, N, p->d_partner + (size_t)k * N, p->d_rs_blocks + p->blk_off[k],
+                            p->blk_per_rank[k], p->block_elems, stream);
+    return st;
+}
+
+int allred_plan_all_gather(allred_plan* p, uint16_t* ranks, uint64_t stride, const uint16_t* in, uint64_t in_stride,
+                           void* workspace, void* stream) {
+    (void)workspace;
+    int st = rs_ag_check(p, ranks, stride, in, in_stride);
+    if (st != ALLRED_OK) return st;
+    const int N = p->total, steps = p->sched.steps;
+    if (N == 1 && !in) return ALLRED_OK;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    if (p->desc.exec == ALLRED_EXEC_FUSED) return launch_all_gather(ranks, stride, p->n, N, in, in_stride, stream);
+    for (int k = steps - 1; k >= 0 && st == ALLRED_OK; --k)
+        st = launch_ag_step(ranks, stride, N, p->d_partner + (size_t)k * N, p->d_ag_blocks + p->blk_off[k],
+                            p->blk_per_rank[k], p->block_elems, stream);
+    return st;
+}
+
 int allred_bf16_add(uint16_t* dst, const uint16_t* src, size_t n, void* stream) {
     return launch_bf16_add(dst, src, n, stream);
 }

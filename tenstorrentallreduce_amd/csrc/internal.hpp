@@ -74,6 +74,13 @@ int launch_tree_reduce(const uint16_t* ranks, uint64_t stride, size_t n, int tot
                        const uint8_t* order, uint16_t* out, void* stream);
 int launch_broadcast(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* src,
                      void* stream);
+// the halves of the fused BO pass as passes of their own (rs_ag_kernels.hip): block b = tree b
+// (order: the plan's P x 64 tree_order table) to rank b's row, or to out + b * out_stride when
+// out is non-null; block b of rank b (or of in + b * in_stride) to every rank's row
+int launch_reduce_scatter(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint8_t* order, uint16_t* out,
+                          uint64_t out_stride, void* stream);
+int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* in, uint64_t in_stride,
+                      void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
