@@ -246,9 +246,9 @@ int allred_plan_execute(allred_plan* plan, uint16_t* ranks, uint64_t rank_stride
  * (+ compute_kernel.cpp:35-67).  In place (out == NULL): block b of rank b's row receives the
  * value the BO allreduce gives block b: tree b of the schedule (tree_order[b]), every add
  * rounded to bf16 — the bits allred_plan_execute leaves there.
- *   ALLRED_EXEC_FUSED plan: one HBM pass (k_rs_reg / k_rs_lds / k_rs_pipe) that writes nothing
- *     else: every other element of every row, and everything past element n of a row, keeps
- *     its bits.
+ *   ALLRED_EXEC_FUSED plan: one HBM pass — the one-row tree pass with a per-block destination,
+ *     k_tree / k_tree_lds / k_tree_lds_pipe with WRITE_ALL = false — that writes nothing else:
+ *     every other element of every row, and everything past element n of a row, keeps its bits.
  *   ALLRED_EXEC_STEPS plan: the reference's reduce-scatter loop alone, one launch per step
  *     k = 0 .. S-1 (whatever the tune key steps_form says).  The blocks a rank does not own
  *     are left holding the reference's partial sums: UNSPECIFIED.  Nothing past element n of

@@ -65,6 +65,40 @@ __device__ __forceinline__ uint4 shfl_xor4(uint4 v, int m) {
     return o;
 }
 
+// ---------------------------------------------------------------------------
+// The BO tree, once.  Block b's result is a binary tree over the P ranks: its
+// leaves are the ranks in the order order[b], level k adds adjacent groups of
+// 2^k leaves, and every add is rounded to bf16 — so the operand order below
+// (the left group is the left operand) fixes the bits, and bit-exact parity
+// with the oracle rests on it.
+// ---------------------------------------------------------------------------
+// the levels inside one lane's N adjacent leaves: x[0] = their subtree's sum
+template <int N>
+__device__ __forceinline__ void tree_levels(uint4 (&x)[N]) {
+#pragma unroll
+    for (int s = 1; s < N; s *= 2)
+#pragma unroll
+        for (int i = 0; i < N; i += 2 * s) x[i] = add8(x[i], x[i + s]);
+}
+
+// A wave's share of a tile's tree (tile rows = ranks, TV 16-byte columns each,
+// lane = half * 32 + column c): this lane's LPL adjacent leaves ord[0 .. LPL)
+// of column c in registers, then the level across the wave's two lane halves.
+template <int TV, int LPL>
+__device__ __forceinline__ uint4 tree_wave_part(const uint4* tile, const uint8_t* ord, int c) {
+    uint4 x[LPL];
+#pragma unroll
+    for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
+    tree_levels(x);
+    return add8(x[0], shfl_xor4(x[0], 32));
+}
+
+// the top two levels: the four waves' partials of column c (rows of pitch TV)
+template <int TV>
+__device__ __forceinline__ uint4 tree_join4(const uint4* part, int c) {
+    return add8(add8(part[0 * TV + c], part[1 * TV + c]), add8(part[2 * TV + c], part[3 * TV + c]));
+}
+
 // Streaming (nontemporal) 16-byte accesses: every byte of a bucket is read
 // once and written once per pass, so nothing is worth keeping in L2 / MALL
 // (measured: the fused tree pass 19.2 -> 16.0 us, the tile-sum 5.9 -> 6.4 TB/s).

@@ -351,7 +351,9 @@ void host_tree_reduce(const uint16_t* ranks, size_t stride, size_t n, const allr
     }
 }
 
-// device copy of tree_order[0] of a (algo, side, total) schedule, cached for the process
+// device copy of the tree order of a (algo, side, total) schedule, cached for the process.  Its callers
+// reduce tree 0 (row 0); all `total` rows are there because the persistent one-row kernel
+// (k_tree_lds_pipe<P, false>) stages the P rows of the table whichever row it then uses
 std::mutex g_order_mu;
 std::map<std::tuple<int, int, int, int>, uint8_t*> g_orders;
 
@@ -366,8 +368,9 @@ int device_order(int algo, int side, int total, const uint8_t** out) {
         int st = build_schedule(algo, side, total, &s, nullptr);
         if (st != ALLRED_OK) return st;
         uint8_t* p = nullptr;
-        if (hipMalloc((void**)&p, ALLRED_MAX_NODES) != hipSuccess) return ALLRED_ERR_NOMEM;
-        if (hipMemcpy(p, s.tree_order[0], ALLRED_MAX_NODES, hipMemcpyHostToDevice) != hipSuccess) return ALLRED_ERR_HIP;
+        const size_t bytes = (size_t)s.total * ALLRED_MAX_NODES;
+        if (hipMalloc((void**)&p, bytes) != hipSuccess) return ALLRED_ERR_NOMEM;
+        if (hipMemcpy(p, s.tree_order[0], bytes, hipMemcpyHostToDevice) != hipSuccess) return ALLRED_ERR_HIP;
         it = g_orders.emplace(key, p).first;
     }
     *out = it->second;

@@ -74,9 +74,10 @@ int launch_tree_reduce(const uint16_t* ranks, uint64_t stride, size_t n, int tot
                        const uint8_t* order, uint16_t* out, void* stream);
 int launch_broadcast(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* src,
                      void* stream);
-// the halves of the fused BO pass as passes of their own (rs_ag_kernels.hip): block b = tree b
+// the halves of the fused BO pass as passes of their own (kernels.hip).  The reduce-scatter is
+// the one-row tree pass of launch_tree_reduce with a per-block destination: block b = tree b
 // (order: the plan's P x 64 tree_order table) to rank b's row, or to out + b * out_stride when
-// out is non-null; block b of rank b (or of in + b * in_stride) to every rank's row
+// out is non-null.  The all-gather: block b of rank b (or of in + b * in_stride) to every rank's row
 int launch_reduce_scatter(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint8_t* order, uint16_t* out,
                           uint64_t out_stride, void* stream);
 int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* in, uint64_t in_stride,
@@ -159,7 +160,8 @@ struct PeerProg {
     uint64_t base[kPeerMaxChannels] = {}, len[kPeerMaxChannels] = {};  // channel slice, 16-byte vectors
 };
 int peer_prog(const allred_dist_desc* d, int rank, PeerProg* out);
-// device copy of tree_order[0] of a (algo, side, total) schedule (cached per device)
+// device copy of the tree order of a (algo, side, total) schedule, all `total` rows (cached per
+// device); its callers reduce tree 0, row 0
 int local_tree_order(int algo, int side, int total, const uint8_t** out);
 
 int launch_peer_allreduce(uint16_t* const* wins, uint32_t* const* flags, int nranks, int me, uint16_t* bucket,

@@ -14,6 +14,7 @@
 // one GPU's HBM, where a "send" is a load of the partner's bytes.
 // Kernel selection is fixed (the measured product forms);
 // allred_tune_set (tune.cpp) switches between bit-identical forms for A/B.
+#include <type_traits>
 #include <utility>
 
 #include "device.hpp"
@@ -65,8 +66,11 @@ __global__ __launch_bounds__(kBlock) void k_add_segs(uint4* __restrict__ dst, co
 // reference's reduce-scatter computes at b's owner: a binary tree whose leaf
 // order is order[b] (allred_schedule.tree_order, row stride 64) and whose
 // level-k nodes add adjacent groups of 2^k leaves, each add rounded to bf16.
-// The all-gather then copies it to every rank, so the pass stores it to all.
-// block_vec == 0 selects row 0 for the whole vector (hierarchical partials).
+// The all-gather then copies it to every rank, so the pass (WRITE_ALL) stores
+// it to all.  The one-row forms (WRITE_ALL = false) store it once, through
+// tree_dst: they are the reduce-scatter, and — block_vec == 0: tree 0 over the
+// whole vector, to `out` — the hierarchical partial, the reduce-scatter of one
+// block.
 //
 // Lane layout (P = 64): lane = g * CH + c.  The 8 lanes of chunk column c
 // each load 8 leaves (ranks order[b][8g .. 8g+7]) of the same 16-byte chunk,
@@ -75,10 +79,28 @@ __global__ __launch_bounds__(kBlock) void k_add_segs(uint4* __restrict__ dst, co
 // to its own 8 ranks.  Each rank's chunk is read and written by one lane only,
 // so the pass is safe in place.  (Shapes the LDS forms below do not take.)
 // ---------------------------------------------------------------------------
+// where the one-row forms put result vector v (16-byte index in a rank row) of
+// block b: block b of `out` (blocks out_stride elements apart), or, out ==
+// nullptr, rank b's own row (the reduce-scatter in place).  block_vec == 0:
+// b == 0, out + v.
+__device__ __forceinline__ uint4* tree_dst(uint16_t* ranks, uint64_t stride, uint16_t* out, uint64_t out_stride,
+                                           uint64_t b, uint64_t v, uint64_t block_vec) {
+    return out ? reinterpret_cast<uint4*>(out + b * out_stride) + (v - b * block_vec)
+               : reinterpret_cast<uint4*>(ranks + b * stride) + v;
+}
+
+// The block, its order row and (one-row form) its destination are PER LANE:
+// with blocks shorter than a wave's CH chunks the lanes of one wave fall into
+// different blocks.  (All lanes of a column share v, hence b, so the shuffles
+// combine one block's leaves.)  One-row form: lane g == 0 stores the column.
+// In place, a tile of block b is read (all P rows) and written (row b) by one
+// wave here, by one workgroup in the LDS forms, and every load of the tile has
+// landed before the store goes out (its data depends on them through the
+// shuffles, or a barrier stands between); no other workgroup touches the tile.
 template <int P, bool WRITE_ALL>
 __global__ __launch_bounds__(kBlock) void k_tree(uint16_t* __restrict__ ranks, uint64_t stride, uint64_t n_vec,
                                                  const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                 uint16_t* __restrict__ out) {
+                                                 uint16_t* __restrict__ out, uint64_t out_stride) {
     constexpr int LEAVES = P >= 8 ? 8 : P;  // leaves per lane
     constexpr int LANES = P / LEAVES;        // lanes per chunk
     constexpr int CH = 64 / LANES;           // chunks per wave
@@ -102,10 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_tree(uint16_t* __restrict__ ranks, u
         uint4 x[LEAVES];
 #pragma unroll
         for (int i = 0; i < LEAVES; ++i) x[i] = ok ? ld_nt(rows[i] + v) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int w = 1; w < LEAVES; w *= 2)
-#pragma unroll
-            for (int i = 0; i < LEAVES; i += 2 * w) x[i] = add8(x[i], x[i + w]);
+        tree_levels(x);
         uint4 acc = x[0];
 #pragma unroll
         for (int m = CH; m < 64; m *= 2) acc = add8(acc, shfl_xor4(acc, m));
@@ -114,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_tree(uint16_t* __restrict__ ranks, u
 #pragma unroll
                 for (int i = 0; i < LEAVES; ++i) st_nt(rows[i] + v, acc);
             } else if (g == 0) {
-                reinterpret_cast<uint4*>(out)[v] = acc;
+                st_nt(tree_dst(ranks, stride, out, out_stride, b, v, block_vec), acc);
             }
         }
     }
@@ -135,14 +154,14 @@ __global__ __launch_bounds__(kBlock) void k_tree(uint16_t* __restrict__ ranks, u
 template <int P, bool WRITE_ALL>
 __global__ __launch_bounds__(kBlock) void k_tree_lds(uint16_t* __restrict__ ranks, uint64_t stride,
                                                      const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                     uint16_t* __restrict__ out) {
+                                                     uint16_t* __restrict__ out, uint64_t out_stride) {
     constexpr int TV = 32;          // 16-byte vectors per rank row of a tile
     constexpr int RPW = P / 4;      // ranks staged (and tree leaves reduced) per wave
     constexpr int LPL = RPW / 2;    // leaves per lane
     __shared__ __attribute__((aligned(16))) uint4 tile[P * TV];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
-    const uint64_t v0 = (uint64_t)blockIdx.x * TV;
+    const uint64_t v0 = (uint64_t)blockIdx.x * TV, b = block_vec ? v0 / block_vec : 0;
 #pragma unroll
     for (int k = 0; k < RPW / 2; ++k) {
         const int r = RPW * w + 2 * k + h;
@@ -151,23 +170,15 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds(uint16_t* __restrict__ rank
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    const uint8_t* ord = order + (block_vec ? v0 / block_vec : 0) * ALLRED_MAX_NODES + RPW * w + LPL * h;
-    uint4 x[LPL];
-#pragma unroll
-    for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
-#pragma unroll
-    for (int s = 1; s < LPL; s *= 2)
-#pragma unroll
-        for (int i = 0; i < LPL; i += 2 * s) x[i] = add8(x[i], x[i + s]);
-    const uint4 part = add8(x[0], shfl_xor4(x[0], 32));
+    const uint4 part = tree_wave_part<TV, LPL>(tile, order + b * ALLRED_MAX_NODES + RPW * w + LPL * h, c);
     __syncthreads();
     if (h == 0) tile[w * TV + c] = part;
     __syncthreads();
-    const uint4 res = add8(add8(tile[0 * TV + c], tile[1 * TV + c]), add8(tile[2 * TV + c], tile[3 * TV + c]));
-    if (!WRITE_ALL) {  // hierarchical partial: one row out
-        if (w == 0 && h == 0) st_nt(reinterpret_cast<uint4*>(out) + v0 + c, res);
+    if (!WRITE_ALL) {  // one row out: one 512-byte store of the tile from the first 32 lanes
+        if (w == 0 && h == 0) st_nt(tree_dst(ranks, stride, out, out_stride, b, v0 + c, block_vec), tree_join4<TV>(tile, c));
         return;
     }
+    const uint4 res = tree_join4<TV>(tile, c);
 #pragma unroll
     for (int k = 0; k < RPW / 2; ++k) {
         const int r = RPW * w + 2 * k + h;
@@ -181,17 +192,20 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds(uint16_t* __restrict__ rank
 // is an exact vmcnt that leaves tile j-1's stores in flight.  Used on pinned
 // HOST buckets (zero-copy end to end: both PCIe directions run at once), for
 // 8 / 16 / 32-rank buckets on HBM, and (WRITE_ALL = false) for the
-// hierarchical partial: the tree of every tile goes to `out` (one row; wave 0
-// keeps its one partial store in flight, the other waves wait for their loads
-// alone).  Tiles of a workgroup are blockIdx.x + j * G, so the workgroups in
-// flight together read adjacent 512-byte segments of every rank row (a
-// contiguous run per workgroup measured 18.8 vs 15.6 us: DRAM page locality
-// across workgroups is what counts).
+// reduce-scatter and the hierarchical partial: the tree of every tile goes to
+// tree_dst (one row; wave 0 issues the one result store per tile and keeps tile
+// j-1's in flight across the wait for tile j's loads — vmcnt(1): the store went
+// out after them —, the other waves have nothing but tile j's loads in flight).
+// Tiles of a workgroup are blockIdx.x + j * G, so the workgroups in flight
+// together read adjacent 512-byte segments of every rank row (a contiguous run
+// per workgroup measured 18.8 vs 15.6 us: DRAM page locality across workgroups
+// is what counts).
 // ---------------------------------------------------------------------------
 template <int P, bool WRITE_ALL = true>
 __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__ ranks, uint64_t stride,
                                                           const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                          uint64_t ntiles, uint16_t* __restrict__ out) {
+                                                          uint64_t ntiles, uint16_t* __restrict__ out,
+                                                          uint64_t out_stride) {
     constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
     static_assert(OPS >= 1, "P >= 8");
     __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
@@ -216,36 +230,40 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
         reinterpret_cast<uint4*>(ord_lds)[i] = reinterpret_cast<const uint4*>(order)[i];
     __syncthreads();
     if (mine > 0) issue(blockIdx.x, 0);
-    for (int j = 0; j < mine; ++j) {
-        if (WRITE_ALL) wait_tile<OPS, 1>(j < 1 ? j : 1);
-        else if (j > 0 && w == 0) wait_vm<1>();   // tile j-1's partial store may stay in flight
-        else wait_vm<0>();
-        lds_barrier();
-        if (j + 1 < mine) issue(blockIdx.x + (uint64_t)(j + 1) * G, (j + 1) & 1);
-        const uint4* tile = buf[j & 1];
-        const uint64_t v0 = (blockIdx.x + (uint64_t)j * G) * TV;
-        const uint8_t* ord = ord_lds + (block_vec ? v0 / block_vec : 0) * ALLRED_MAX_NODES + RPW * w + LPL * q;
-        uint4 x[LPL];
+    // The tile loop.  A workgroup has one tile's loads in flight while it reduces, so what a tile
+    // costs between their arrival and the next tile's issue shows in the pass's time: the
+    // hierarchical partial (one_block: block_vec == 0, tree 0 to out + v) gets a loop of its own
+    // that carries no block division and no destination arithmetic; every other caller's loop
+    // takes order row and destination from the tile's block.
+    auto tiles = [&](auto one_block) {
+        for (int j = 0; j < mine; ++j) {
+            const uint64_t v0 = (blockIdx.x + (uint64_t)j * G) * TV;
+            const uint64_t b = one_block() ? 0 : (block_vec ? v0 / block_vec : 0);
+            if (WRITE_ALL) wait_tile<OPS, 1>(j < 1 ? j : 1);
+            else if (j > 0 && w == 0) wait_vm<1>();   // tile j-1's result store may stay in flight
+            else wait_vm<0>();
+            lds_barrier();
+            if (j + 1 < mine) issue(blockIdx.x + (uint64_t)(j + 1) * G, (j + 1) & 1);
+            const uint4* tile = buf[j & 1];
+            const uint4 pw = tree_wave_part<TV, LPL>(tile, ord_lds + b * ALLRED_MAX_NODES + RPW * w + LPL * q, c);
+            if (q == 0) part[w * TV + c] = pw;
+            lds_barrier();
+            if (!WRITE_ALL) {
+                if (w == 0 && q == 0) st_nt(one_block() ? reinterpret_cast<uint4*>(out) + v0 + c : tree_dst(ranks, stride, out, out_stride, b, v0 + c, block_vec), tree_join4<TV>(part, c));
+                continue;
+            }
+            const uint4 res = tree_join4<TV>(part, c);
 #pragma unroll
-        for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
-#pragma unroll
-        for (int s = 1; s < LPL; s *= 2)
-#pragma unroll
-            for (int i = 0; i < LPL; i += 2 * s) x[i] = add8(x[i], x[i + s]);
-        const uint4 pw = add8(x[0], shfl_xor4(x[0], 32));   // tree level across the two lane halves
-        if (q == 0) part[w * TV + c] = pw;
-        lds_barrier();
-        const uint4 res = add8(add8(part[0 * TV + c], part[1 * TV + c]), add8(part[2 * TV + c], part[3 * TV + c]));
-        if (!WRITE_ALL) {
-            if (w == 0 && q == 0) st_nt(reinterpret_cast<uint4*>(out) + v0 + c, res);
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < OPS; ++k) {
-            const int r = RPW * w + RPI * k + q;
-            st_nt(reinterpret_cast<uint4*>(ranks + (uint64_t)r * stride) + v0 + c, res);
-        }
+            for (int k = 0; k < OPS; ++k) {
+                const int r = RPW * w + RPI * k + q;
+                st_nt(reinterpret_cast<uint4*>(ranks + (uint64_t)r * stride) + v0 + c, res);
+            }
     }
+    };
+    if constexpr (!WRITE_ALL) {
+        if (block_vec == 0) return tiles(std::true_type{});
+    }
+    tiles(std::false_type{});
 }
 
 // ---------------------------------------------------------------------------
@@ -307,14 +325,7 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_lag(uint16_t* __restrict__ 
         const uint4* tile = buf[j & 1];
         const uint64_t t = tile_of(j), v0 = t * TV;
         const uint8_t* ord = ord_lds + (block_vec ? v0 / block_vec : 0) * ALLRED_MAX_NODES + RPW * w + LPL * q;
-        uint4 x[LPL];
-#pragma unroll
-        for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
-#pragma unroll
-        for (int s = 1; s < LPL; s *= 2)
-#pragma unroll
-            for (int i = 0; i < LPL; i += 2 * s) x[i] = add8(x[i], x[i + s]);
-        const uint4 pw = add8(x[0], shfl_xor4(x[0], 32));   // tree level across the two lane halves
+        const uint4 pw = tree_wave_part<TV, LPL>(tile, ord, c);
         if (q == 0) part[j & 1][w * TV + c] = pw;
         lds_barrier();   // every wave has read tile j out of buf[j & 1]; the partials are in
         {   // tile j+2's loads and tile j-1's stores, interleaved op by op
@@ -327,8 +338,7 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_lag(uint16_t* __restrict__ 
                 if (j >= 1) st_nt(reinterpret_cast<uint4*>(row(k)) + ts * TV + c, prev);
             }
         }
-        const uint4* pp = part[j & 1];
-        prev = add8(add8(pp[0 * TV + c], pp[1 * TV + c]), add8(pp[2 * TV + c], pp[3 * TV + c]));
+        prev = tree_join4<TV>(part[j & 1], c);
     }
     if (mine > 0) {
 #pragma unroll
@@ -425,20 +435,11 @@ __global__ __launch_bounds__(kBlock) void k_tree_bcast_x(uint16_t* __restrict__ 
         const uint4* tile = buf[j & 1];
         const uint64_t t = tile_of(j), v0 = t * TV;
         const uint4 pnew = res_lds[j & 1][c];   // bucket i's result, read before the slot is reloaded
-        const uint8_t* ord = ord_lds + RPW * w + LPL * q;
-        uint4 x[LPL];
-#pragma unroll
-        for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
-#pragma unroll
-        for (int s = 1; s < LPL; s *= 2)
-#pragma unroll
-            for (int i = 0; i < LPL; i += 2 * s) x[i] = add8(x[i], x[i + s]);
-        const uint4 pw = add8(x[0], shfl_xor4(x[0], 32));   // tree level across the two lane halves
+        const uint4 pw = tree_wave_part<TV, LPL>(tile, ord_lds + RPW * w + LPL * q, c);
         if (q == 0) part[j & 1][w * TV + c] = pw;
         lds_barrier();   // tile j and result slot j & 1 are read by every wave; the partials are in
         if (hasr) {
-            const uint4* pp = part[j & 1];
-            const uint4 r = add8(add8(pp[0 * TV + c], pp[1 * TV + c]), add8(pp[2 * TV + c], pp[3 * TV + c]));
+            const uint4 r = tree_join4<TV>(part[j & 1], c);
             if (q == 0 && (!BAL || (c >> 3) == w)) st_nt(reinterpret_cast<uint4*>(cur_partial) + v0 + c, r);
         }
         {   // tile j+2's loads and bucket i's row stores (tile j - LAG), interleaved op by op
@@ -929,6 +930,55 @@ __global__ __launch_bounds__(kBlock) void k_broadcast(uint16_t* __restrict__ ran
     for (uint64_t v = gtid(); v < n_vec; v += gthreads()) {
         const uint4 x = src[v];
         for (int r = r0; r < r1; ++r) st_nt(reinterpret_cast<uint4*>(ranks + (uint64_t)r * stride) + v, x);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// All-gather (the AG loop, allred_BO_2D/kernels/dataflow_kernel.cpp:219-267):
+// block b of rank b (or of in + b * in_stride) copied to block b of every rank,
+// a pure 16-bit copy — k_broadcast's data movement with the source row chosen
+// per block, on a persistent grid.  A wave's item = (64 consecutive 16-byte
+// vectors — two 512-byte tiles —, a group of up to 8 ranks): one load per lane
+// from the vector's block owner (or `in`), then its 8 row stores; the next
+// item's load goes out before the stores, so a wave never waits for a load
+// with an empty store queue.  Items are group-major, so the waves of a
+// workgroup write adjacent kilobytes of the same 8 rows.  The source block and
+// row are per lane: a 64-vector run may cross blocks.  In place the owner's
+// own row is not rewritten; every other row of a vector has exactly one writer
+// and the source vector none, so there is nothing to order.
+// ---------------------------------------------------------------------------
+constexpr int kAgRows = 8;
+
+__global__ __launch_bounds__(kBlock) void k_ag(uint16_t* ranks, uint64_t stride, int total, uint64_t n_vec,
+                                               uint64_t block_vec, const uint16_t* in, uint64_t in_stride,
+                                               uint64_t chunks, uint64_t items) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t waves = (uint64_t)gridDim.x * (kBlock / 64);
+    uint64_t i = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (i >= items) return;
+    auto load = [&](uint64_t item, uint64_t& v, uint64_t& b) {
+        v = (item % chunks) * 64 + lane;
+        b = v < n_vec ? v / block_vec : 0;
+        if (v >= n_vec) return make_uint4(0, 0, 0, 0);
+        return in ? reinterpret_cast<const uint4*>(in + b * in_stride)[v - b * block_vec]
+                  : reinterpret_cast<const uint4*>(ranks + b * stride)[v];
+    };
+    uint64_t v, b, vn = 0, bn = 0;
+    uint4 x = load(i, v, b), xn = make_uint4(0, 0, 0, 0);
+    for (;;) {
+        const uint64_t next = i + waves;
+        const bool more = next < items;
+        if (more) xn = load(next, vn, bn);
+        const int r0 = (int)(i / chunks) * kAgRows;
+        if (v < n_vec) {
+#pragma unroll
+            for (int k = 0; k < kAgRows; ++k) {
+                const int r = r0 + k;
+                if (r < total && (in || (uint64_t)r != b)) st_nt(reinterpret_cast<uint4*>(ranks + (uint64_t)r * stride) + v, x);
+            }
+        }
+        if (!more) break;
+        i = next, v = vn, b = bn, x = xn;
     }
 }
 
@@ -1526,57 +1576,60 @@ int last_error() { return hip_status((int)hipGetLastError()); }
 // fused_form (tune.cpp): 0 auto, 1 register tree, 2 one tile per workgroup, 3 persistent
 inline int64_t fused_form() { return tune(Tune::fused_form); }
 
-template <bool WRITE_ALL>
-int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, const uint8_t* order,
-                  uint64_t block_vec, uint16_t* out, hipStream_t st) {
-    const int64_t form = fused_form();
-    // hierarchical partial of 64 ranks, >= 1024 tiles: the persistent
-    // double-buffered form (2 workgroups per CU), as the fused pass.  (The
-    // early-release / two-tiles-ahead forms measured slower on this read-only
-    // stream: 10.4 / 9.9 vs 9.6 us, profiles/r01_partial_ab.txt.)
-    if (!WRITE_ALL && total == 64 && n_vec % 32 == 0 && block_vec == 0 && form != 1 && form != 2 &&
-        (n_vec / 32 >= 1024 || form == 3)) {
-        const uint64_t tiles = n_vec / 32;
-        hipLaunchKernelGGL((k_tree_lds_pipe<64, false>), dim3((unsigned)(tiles < 512 ? tiles : 512)), dim3(kBlock), 0,
-                           st, ranks, stride, order, (uint64_t)0, tiles, out);
-        return last_error();
+// The rank count as a template argument: f(std::integral_constant<int, total>{}) for a power of
+// two total in [LO, HI]; false (nothing launched) when the kernels have no instance for it.
+template <int LO, int HI, class F>
+bool for_ranks(int total, F&& f) {
+    if (total == LO) {
+        f(std::integral_constant<int, LO>{});
+        return true;
     }
-    // LDS-staged form: whole 32-vector tiles inside one block (any tile when block_vec == 0)
-    if (total >= 8 && n_vec % 32 == 0 && (block_vec == 0 || block_vec % 32 == 0) && (block_vec || !WRITE_ALL) &&
-        form != 1) {
-        const dim3 grid((unsigned)(n_vec / 32)), blk(kBlock);
-        switch (total) {
-            case 8: hipLaunchKernelGGL((k_tree_lds<8, WRITE_ALL>), grid, blk, 0, st, ranks, stride, order, block_vec, out); break;
-            case 16: hipLaunchKernelGGL((k_tree_lds<16, WRITE_ALL>), grid, blk, 0, st, ranks, stride, order, block_vec, out); break;
-            case 32: hipLaunchKernelGGL((k_tree_lds<32, WRITE_ALL>), grid, blk, 0, st, ranks, stride, order, block_vec, out); break;
-            case 64: hipLaunchKernelGGL((k_tree_lds<64, WRITE_ALL>), grid, blk, 0, st, ranks, stride, order, block_vec, out); break;
-            default: return ALLRED_ERR_UNSUPPORTED;
-        }
-        return last_error();
-    }
-    const int lanes = total >= 8 ? total / 8 : 1;
-    const uint64_t chunk_groups = (n_vec + (64 / lanes) - 1) / (64 / lanes);  // one per wave
-    uint64_t blocks = (chunk_groups + 3) / 4;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const dim3 grid((unsigned)blocks), blk(kBlock);
-    switch (total) {
-        case 1: hipLaunchKernelGGL((k_tree<1, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 2: hipLaunchKernelGGL((k_tree<2, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 4: hipLaunchKernelGGL((k_tree<4, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 8: hipLaunchKernelGGL((k_tree<8, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 16: hipLaunchKernelGGL((k_tree<16, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 32: hipLaunchKernelGGL((k_tree<32, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        case 64: hipLaunchKernelGGL((k_tree<64, WRITE_ALL>), grid, blk, 0, st, ranks, stride, n_vec, order, block_vec, out); break;
-        default: return ALLRED_ERR_UNSUPPORTED;
-    }
-    return last_error();
+    if constexpr (LO < HI) return for_ranks<2 * LO, HI>(total, f);
+    return false;
 }
 
 unsigned persistent_grid(uint64_t tiles, uint64_t dflt) {
     const int64_t g = tune(Tune::pipe_grid);
     const uint64_t cap = g > 0 ? (uint64_t)g : dflt;
     return (unsigned)(tiles < cap ? tiles : cap);
+}
+
+// The BO tree pass by shape class.  WRITE_ALL: the fused pass's forms that launch_tree_fused
+// does not take itself.  One row (!WRITE_ALL): the reduce-scatter (block b to out + b *
+// out_stride, or to rank b's row) and the hierarchical partial (block_vec == 0: tree 0 to out).
+template <bool WRITE_ALL>
+int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, const uint8_t* order,
+                  uint64_t block_vec, uint16_t* out, uint64_t out_stride, hipStream_t st) {
+    const int64_t form = fused_form();
+    const uint64_t tiles = n_vec / 32;
+    // whole 32-vector tiles inside one block (any tile when block_vec == 0)
+    const bool whole_tiles = total >= 8 && n_vec % 32 == 0 && block_vec % 32 == 0 && (block_vec || !WRITE_ALL);
+    bool found;
+    // one row of 64 ranks, >= 1024 tiles: the persistent double-buffered form (2 workgroups
+    // per CU), as the fused pass.  (The early-release / two-tiles-ahead forms measured slower
+    // on this read-only stream: 10.4 / 9.9 vs 9.6 us, profiles/r01_partial_ab.txt.)
+    if (!WRITE_ALL && whole_tiles && form != 1 && form != 2 && ((total == 64 && tiles >= 1024) || form == 3)) {
+        found = for_ranks<8, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_tree_lds_pipe<p(), false>), dim3(persistent_grid(tiles, 512)), dim3(kBlock), 0, st,
+                               ranks, stride, order, block_vec, tiles, out, out_stride);
+        });
+    } else if (whole_tiles && form != 1) {   // one tile per workgroup, staged in LDS
+        found = for_ranks<8, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_tree_lds<p(), WRITE_ALL>), dim3((unsigned)tiles), dim3(kBlock), 0, st, ranks, stride,
+                               order, block_vec, out, out_stride);
+        });
+    } else {   // the register form: fewer than 8 ranks, and buckets that are not whole tiles
+        const int lanes = total >= 8 ? total / 8 : 1;
+        const uint64_t chunk_groups = (n_vec + (64 / lanes) - 1) / (64 / lanes);  // one per wave
+        uint64_t blocks = (chunk_groups + 3) / 4;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        found = for_ranks<1, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_tree<p(), WRITE_ALL>), dim3((unsigned)blocks), dim3(kBlock), 0, st, ranks, stride,
+                               n_vec, order, block_vec, out, out_stride);
+        });
+    }
+    return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
 }
 
 // the schedule form with register-staged strips (k_steps_reg): 8..64 ranks; false if the shape has no instance.
@@ -1591,25 +1644,26 @@ bool launch_steps_reg(bool bo, int per_cu, uint16_t* ranks, uint64_t stride, int
     const int64_t early = tune(Tune::steps_early);
     const bool early_on = early == 2 || (early == 1 && units >= 256 * (uint64_t)per_cu);
     const int flags = (tune(Tune::steps_tab) ? 1 : 0) | (early_on ? 2 : 0);
-#define TSA_SR(PP, BOV, MW) do { \
-        hipLaunchKernelGGL((k_steps_reg<PP, BOV, MW>), grid, dim3(256), 0, st, ranks, stride, tab, pairs, bv, slices, \
-                           units, stamps, flags); \
-        note_launch(reinterpret_cast<const void*>(&k_steps_reg<PP, BOV, MW>), "k_steps_reg<" #PP ", " #BOV ", " #MW ">", \
-                    grid.x, 256); \
-    } while (0)
-#define TSA_SRB(PP, BOV) do { if (per_cu >= 5) TSA_SR(PP, BOV, 5); else if (per_cu == 4) TSA_SR(PP, BOV, 4); \
-                              else TSA_SR(PP, BOV, 3); } while (0)
-#define TSA_SRP(PP) do { if (bo) TSA_SRB(PP, true); else TSA_SRB(PP, false); } while (0)
-    switch (total) {
-        case 8: TSA_SRP(8); return true;
-        case 16: TSA_SRP(16); return true;
-        case 32: TSA_SRP(32); return true;
-        case 64: TSA_SRP(64); return true;
-        default: return false;
-    }
-#undef TSA_SRP
-#undef TSA_SRB
-#undef TSA_SR
+#define TSA_SR_NAMES(PP, BOV) \
+    {"k_steps_reg<" #PP ", " #BOV ", 3>", "k_steps_reg<" #PP ", " #BOV ", 4>", "k_steps_reg<" #PP ", " #BOV ", 5>"}
+    static const char* const names[2][4][3] = {   // [BO][log2(P) - 3][MINW - 3]
+        {TSA_SR_NAMES(8, false), TSA_SR_NAMES(16, false), TSA_SR_NAMES(32, false), TSA_SR_NAMES(64, false)},
+        {TSA_SR_NAMES(8, true), TSA_SR_NAMES(16, true), TSA_SR_NAMES(32, true), TSA_SR_NAMES(64, true)}};
+#undef TSA_SR_NAMES
+    return for_ranks<8, 64>(total, [&](auto p) {
+        auto with = [&](auto is_bo, auto minw) {
+            constexpr auto kern = &k_steps_reg<p(), is_bo(), minw()>;
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, ranks, stride, tab, pairs, bv, slices, units, stamps, flags);
+            note_launch(reinterpret_cast<const void*>(kern), names[is_bo()][log2_of<p()>() - 3][minw() - 3], grid.x, 256);
+        };
+        auto with_bo = [&](auto is_bo) {
+            if (per_cu >= 5) with(is_bo, std::integral_constant<int, 5>{});
+            else if (per_cu == 4) with(is_bo, std::integral_constant<int, 4>{});
+            else with(is_bo, std::integral_constant<int, 3>{});
+        };
+        if (bo) with_bo(std::true_type{});
+        else with_bo(std::false_type{});
+    });
 }
 
 }  // namespace
@@ -1711,16 +1765,14 @@ int launch_tree_fused(uint16_t* ranks, uint64_t stride, size_t n, int total, con
     // directions busy, tools/pcie_probe.py), or forced persistent form
     if (whole_tiles && (host_memory || form == 3)) {
         const unsigned grid = persistent_grid(tiles, host_memory ? 32 : 512);
-        switch (total) {
-            case 8: hipLaunchKernelGGL((k_tree_lds_pipe<8>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv, tiles, nullptr); break;
-            case 16: hipLaunchKernelGGL((k_tree_lds_pipe<16>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv, tiles, nullptr); break;
-            case 32: hipLaunchKernelGGL((k_tree_lds_pipe<32>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv, tiles, nullptr); break;
-            case 64: hipLaunchKernelGGL((k_tree_lds_pipe<64>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv, tiles, nullptr); break;
-            default: return ALLRED_ERR_UNSUPPORTED;
-        }
+        const bool found = for_ranks<8, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_tree_lds_pipe<p(), true>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv,
+                               tiles, nullptr, (uint64_t)0);
+        });
+        if (!found) return ALLRED_ERR_UNSUPPORTED;
         return last_error();
     }
-    return tree_dispatch<true>(ranks, stride, nv, total, order, bv, nullptr, st);
+    return tree_dispatch<true>(ranks, stride, nv, total, order, bv, nullptr, 0, st);
 }
 
 int launch_lo_dag_reg(uint16_t* ranks, uint64_t stride, size_t n, int algo, int side, int total, void* stream) {
@@ -1777,28 +1829,33 @@ int launch_butterfly(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
     if (blocks < 1) blocks = 1;
     if (blocks > 256 * 16) blocks = 256 * 16;
     const dim3 grid((unsigned)blocks), blk(kBlock);
-#define TSA_BFLY(PP)                                                                                          \
-    if (small) hipLaunchKernelGGL((k_butterfly<PP, 1>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps); \
-    else hipLaunchKernelGGL((k_butterfly<PP, 8>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps);
-    switch (total) {
-        case 1: return ALLRED_OK;  // one rank: nothing to reduce
-        case 2: TSA_BFLY(2) break;
-        case 4: TSA_BFLY(4) break;
-        case 8: TSA_BFLY(8) break;
-        case 16: TSA_BFLY(16) break;
-        case 32: TSA_BFLY(32) break;
-        case 64: TSA_BFLY(64) break;
-        default: return ALLRED_ERR_UNSUPPORTED;
-    }
-#undef TSA_BFLY
+    if (total == 1) return ALLRED_OK;  // one rank: nothing to reduce
+    const bool found = for_ranks<2, 64>(total, [&](auto p) {
+        if (small) hipLaunchKernelGGL((k_butterfly<p(), 1>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps);
+        else hipLaunchKernelGGL((k_butterfly<p(), 8>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps);
+    });
+    if (!found) return ALLRED_ERR_UNSUPPORTED;
     return last_error();
 }
 
 int launch_tree_reduce(const uint16_t* ranks, uint64_t stride, size_t n, int total, const uint8_t* order,
                        uint16_t* out, void* stream) {
     if (n % 8 || stride % 8 || !aligned16(ranks) || !aligned16(out)) return ALLRED_ERR_ARG;
-    return tree_dispatch<false>(const_cast<uint16_t*>(ranks), stride, n / 8, total, order, 0, out,
+    // block_vec == 0: tree 0 over the whole vector, to out
+    return tree_dispatch<false>(const_cast<uint16_t*>(ranks), stride, n / 8, total, order, 0, out, 0,
                                 (hipStream_t)stream);
+}
+
+// The reduce-scatter half of the BO allreduce as a pass of its own (the RS loop of
+// allred_BO_2D/kernels/dataflow_kernel.cpp:152-213 + compute_kernel.cpp:35-67): the one-row
+// tree pass with a per-block destination — block b to rank b's row (out == nullptr) or to
+// out + b * out_stride.  Reads the P rank rows and writes ONE row's worth: (P + 1) n bytes.
+int launch_reduce_scatter(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint8_t* order, uint16_t* out,
+                          uint64_t out_stride, void* stream) {
+    if (total < 1 || n == 0 || n % (8 * (size_t)total) || stride % 8 || !aligned16(ranks) ||
+        (out && (out_stride % 8 || !aligned16(out))))
+        return ALLRED_ERR_ARG;
+    return tree_dispatch<false>(ranks, stride, n / 8, total, order, n / 8 / total, out, out_stride, (hipStream_t)stream);
 }
 
 int launch_tree_bcast_x(uint16_t* cur, uint16_t* prev, uint64_t stride, size_t n, int total, const uint8_t* order,
@@ -1832,6 +1889,25 @@ int launch_broadcast(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
     const uint64_t nv = n / 8;
     hipLaunchKernelGGL(k_broadcast, dim3(grid_all(nv), (total + 7) / 8), dim3(kBlock), 0, (hipStream_t)stream, ranks,
                        stride, total, reinterpret_cast<const uint4*>(src), nv);
+    return last_error();
+}
+
+// one kernel for every shape: its items are 64-vector runs whatever the block size
+int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* in, uint64_t in_stride,
+                      void* stream) {
+    if (total < 1 || total > ALLRED_MAX_NODES || n == 0 || n % (8 * (size_t)total) || stride % 8 || !aligned16(ranks) ||
+        (in && (in_stride % 8 || !aligned16(in))))
+        return ALLRED_ERR_ARG;
+    const uint64_t nv = n / 8, bv = nv / total, chunks = (nv + 63) / 64;
+    const uint64_t items = chunks * (uint64_t)((total + kAgRows - 1) / kAgRows);
+    // a resident grid (at most 8 four-wave workgroups per CU; tune pipe_grid caps it lower) sized so
+    // that every wave gets the same number of items: a fixed 512 workgroups left config 2's 5120
+    // items at 2 or 3 per wave, 7.96 us against k_broadcast's 7.58 in the same run
+    const uint64_t groups = (items + 3) / 4, cap = persistent_grid(kMaxGrid, kMaxGrid);
+    const uint64_t per = (groups + cap - 1) / cap;
+    const dim3 grid((unsigned)((groups + per - 1) / per));
+    hipLaunchKernelGGL(k_ag, grid, dim3(kBlock), 0, (hipStream_t)stream, ranks, stride, total, nv, bv, in, in_stride,
+                       chunks, items);
     return last_error();
 }
 
@@ -1950,13 +2026,9 @@ int mem_reduce_impl(uint16_t* r, uint64_t stride, uint64_t nv, int total, uint16
     // column), profiles/r01_mem_reduce_ab.txt
     if (tune(Tune::mem_reduce_lds) && bv % 32 == 0 && total >= 4 && total <= 64 && (total & (total - 1)) == 0) {
         const dim3 grid((unsigned)(nv / 32)), blk(128);
-        switch (total) {
-            case 4: hipLaunchKernelGGL((k_mem_lds<4, ACC16>), grid, blk, 0, st, r, stride, bv, dst); break;
-            case 8: hipLaunchKernelGGL((k_mem_lds<8, ACC16>), grid, blk, 0, st, r, stride, bv, dst); break;
-            case 16: hipLaunchKernelGGL((k_mem_lds<16, ACC16>), grid, blk, 0, st, r, stride, bv, dst); break;
-            case 32: hipLaunchKernelGGL((k_mem_lds<32, ACC16>), grid, blk, 0, st, r, stride, bv, dst); break;
-            default: hipLaunchKernelGGL((k_mem_lds<64, ACC16>), grid, blk, 0, st, r, stride, bv, dst); break;
-        }
+        for_ranks<4, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_mem_lds<p(), ACC16>), grid, blk, 0, st, r, stride, bv, dst);
+        });
         return last_error();
     }
     // one column per thread reads all `total` ranks, sixteen ranks' loads in
@@ -1980,14 +2052,10 @@ int mem_fused_impl(uint16_t* ranks, uint64_t stride, uint64_t nv, int total, hip
     }
     if (bv % 32 == 0 && total >= 4 && fused_form() != 1) {
         const dim3 grid((unsigned)tiles), blk(128);
-        switch (total) {
-            case 4: hipLaunchKernelGGL((k_mem_lds<4, ACC16>), grid, blk, 0, st, ranks, stride, bv, nullptr); return last_error();
-            case 8: hipLaunchKernelGGL((k_mem_lds<8, ACC16>), grid, blk, 0, st, ranks, stride, bv, nullptr); return last_error();
-            case 16: hipLaunchKernelGGL((k_mem_lds<16, ACC16>), grid, blk, 0, st, ranks, stride, bv, nullptr); return last_error();
-            case 32: hipLaunchKernelGGL((k_mem_lds<32, ACC16>), grid, blk, 0, st, ranks, stride, bv, nullptr); return last_error();
-            case 64: hipLaunchKernelGGL((k_mem_lds<64, ACC16>), grid, blk, 0, st, ranks, stride, bv, nullptr); return last_error();
-            default: break;
-        }
+        const bool found = for_ranks<4, 64>(total, [&](auto p) {
+            hipLaunchKernelGGL((k_mem_lds<p(), ACC16>), grid, blk, 0, st, ranks, stride, bv, (uint16_t*)nullptr);
+        });
+        if (found) return last_error();
     }
     hipLaunchKernelGGL((k_mem<true, 8, ACC16>), dim3(grid_for(nv)), dim3(kBlock), 0, st, ranks, stride, total, nv, bv,
                        nullptr);

@@ -746,10 +746,7 @@ __global__ __launch_bounds__(128 * (32 / CW), (CW == 8 ? 4 : CW == 16 ? 2 : 1)) 
                 const uint32_t leaf = (ob[i / 4] >> (8 * (i & 3))) & 255u;
                 x[i] = tile[(int)leaf * CW + cc];
             }
-#pragma unroll
-            for (int s2 = 1; s2 < LPL; s2 *= 2)
-#pragma unroll
-                for (int i = 0; i < LPL; i += 2 * s2) x[i] = add8(x[i], x[i + s2]);
+            tree_levels(x);
 #pragma unroll
             for (int m = CW; m < 64; m *= 2) x[0] = add8(x[0], shfl_xor4(x[0], m));
             const uint4 pr = CW == 32 ? x[0] : shfl4(x[0], cc);   // leaf group 0's sum: k_hier_x2's operand order
@@ -997,15 +994,7 @@ __global__ __launch_bounds__(kBlock) void k_hier_x2(uint16_t* __restrict__ cur, 
                      (j >= 1 && w < 3 ? 1 : 0));
             lds_barrier();   // tile j is in LDS
             const uint4* tile = buf[j & 1];
-            const uint8_t* ord = ord_lds + RPW * w + LPL * q;
-            uint4 x[LPL];
-#pragma unroll
-            for (int i = 0; i < LPL; ++i) x[i] = tile[(int)ord[i] * TV + c];
-#pragma unroll
-            for (int s2 = 1; s2 < LPL; s2 *= 2)
-#pragma unroll
-                for (int i = 0; i < LPL; i += 2 * s2) x[i] = add8(x[i], x[i + s2]);
-            const uint4 pw = add8(x[0], shfl_xor4(x[0], 32));
+            const uint4 pw = tree_wave_part<TV, LPL>(tile, ord_lds + RPW * w + LPL * q, c);
             if (q == 0) part[j & 1][w * TV + c] = pw;
             lds_barrier();   // partials in; every wave has read tile j out of buf[j & 1]
             // old's results of chunks 0 (and 1), ahead of this launch's first partial push (the
@@ -1028,8 +1017,7 @@ __global__ __launch_bounds__(kBlock) void k_hier_x2(uint16_t* __restrict__ cur, 
             if (q == 0) {
                 const uint64_t t = tile_of(j);
                 const int o = owner_of(t);
-                const uint4* pp = part[j & 1];
-                const uint4 pr = add8(add8(pp[0 * TV + c], pp[1 * TV + c]), add8(pp[2 * TV + c], pp[3 * TV + c]));
+                const uint4 pr = tree_join4<TV>(part[j & 1], c);
                 const uint64_t slot = (t - (uint64_t)o * tiles_per_owner) * W + me;
                 if (w < 3)
                     __hip_atomic_store(lc.ll[o] + slot * kHSlot + 32 * w + c, h_pack(pr, w, e8c), __ATOMIC_RELAXED,

@@ -3,6 +3,8 @@ one device, so N>1 is covered by test_dist_host.py's identical step program
 over gloo and by the driver's multi-GPU run).  Checks communicator setup and
 the hierarchical stages (on-GPU tree reduce + broadcast) against the host
 twin and the oracle, bit for bit."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -33,6 +35,47 @@ def test_tree_reduce_and_broadcast_match_oracle(n):
     torch.cuda.synchronize()
     got = buf.cpu().numpy().view(np.uint16)
     assert (got == got[0]).all() and np.array_equal(got[0], out.cpu().numpy().view(np.uint16))
+
+
+@functools.lru_cache(maxsize=None)
+def bo_reference(algo, side, total, m):
+    """(inputs (total, total * m), block 0 of the oracle's BO allreduce of them), read-only, computed once"""
+    rng = np.random.default_rng(1000 * total + 10 * algo + m % 97)
+    data = rng.integers(0x3F80, 0x42C8, (total, total * m)).astype(np.uint16)
+    want = [r.copy() for r in data]
+    oracle.allreduce("bo", algo, side, want, total)
+    block0 = want[0][:m].copy()
+    data.flags.writeable = False
+    block0.flags.writeable = False
+    return data, block0
+
+
+# tree_reduce is the one-row tree pass with block_vec == 0: tree 0 over the whole vector, and block
+# 0 of the BO allreduce is tree 0.  The smallest shapes that reach each form: 40 elements = 5
+# vectors (the register form, idle lanes in the last wave); 512 = 2 tiles (8+ ranks: one tile per
+# workgroup); 1280 = 5 tiles under fused_form 3 on a persistent grid of 2 (8+ ranks: 3 and 2 tiles
+# per workgroup, so the first-tile wait and wave 0's "previous store in flight" wait both run)
+TREE_GRIDS = [(1, 1), (2, 2), (2, 4), (4, 8), (4, 16), (8, 32), (8, 64)]
+TREE_CASES = [(a, s, p, m, keys) for s, p in TREE_GRIDS for a in (t.SWING, t.RECDUB)
+              for m, keys in ((40, {}), (512, {}), (1280, {"fused_form": 3, "pipe_grid": 2})) if m == 40 or p >= 8]
+
+
+@pytest.mark.parametrize("algo,side,total,m,keys", TREE_CASES,
+                         ids=[f"algo{a}-{s}x{p}-m{m}" for a, s, p, m, _ in TREE_CASES])
+def test_tree_reduce_is_block_0_of_the_bo_allreduce(algo, side, total, m, keys):
+    """Rows total * m apart, the first m elements of each reduced: bit for bit block 0 of the
+    oracle's BO allreduce; nothing behind `out` written, the ranks only read."""
+    sent, guard = 0xA5A5, 64
+    data, want = bo_reference(algo, side, total, m)
+    buf = torch.from_numpy(data.copy().view(np.int16)).to(DEV)
+    out = torch.from_numpy(np.full(m + guard, sent, dtype=np.uint16).view(np.int16)).to(DEV)
+    with t.tuned(**keys):
+        t.tree_reduce(buf.data_ptr(), total * m, m, algo, side, total, out.data_ptr())
+        torch.cuda.synchronize()
+    got = out.cpu().numpy().view(np.uint16)
+    assert np.array_equal(got[:m], want)
+    assert (got[m:] == sent).all()
+    assert np.array_equal(buf.cpu().numpy().view(np.uint16), data)
 
 
 @pytest.mark.parametrize("local", [1, 64])
