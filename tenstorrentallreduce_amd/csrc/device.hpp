@@ -113,6 +113,16 @@ __device__ __forceinline__ void st_nt(uint4* p, uint4 v) {
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
 }
 
+// A row pointer kept across a loop behind an empty asm (so that it stays in registers) must
+// carry the global address space in its type: the compiler cannot see through the asm that
+// it points to global memory, and a generic pointer's store is a flat_store, which counts
+// on lgkmcnt as well as vmcnt.
+typedef __attribute__((address_space(1))) u32x4 global_u32x4;
+__device__ __forceinline__ void st_nt(global_u32x4* p, uint4 v) {
+    const u32x4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, p);
+}
+
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(1))) const uint32_t global_u32;
 

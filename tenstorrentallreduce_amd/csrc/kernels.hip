@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "device.hpp"
+#include "tile_span.hpp"
 
 namespace tsa {
 namespace {
@@ -154,14 +155,15 @@ __global__ __launch_bounds__(kBlock) void k_tree(uint16_t* __restrict__ ranks, u
 template <int P, bool WRITE_ALL>
 __global__ __launch_bounds__(kBlock) void k_tree_lds(uint16_t* __restrict__ ranks, uint64_t stride,
                                                      const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                     uint16_t* __restrict__ out, uint64_t out_stride) {
+                                                     TileSpan span, uint16_t* __restrict__ out, uint64_t out_stride) {
     constexpr int TV = 32;          // 16-byte vectors per rank row of a tile
     constexpr int RPW = P / 4;      // ranks staged (and tree leaves reduced) per wave
     constexpr int LPL = RPW / 2;    // leaves per lane
     __shared__ __attribute__((aligned(16))) uint4 tile[P * TV];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
-    const uint64_t v0 = (uint64_t)blockIdx.x * TV, b = block_vec ? v0 / block_vec : 0;
+    // one tile per workgroup: its block by the host's reciprocal (tile_span.hpp), no division
+    const uint64_t v0 = (uint64_t)blockIdx.x * TV, b = tile_span_first(span, blockIdx.x).block;
 #pragma unroll
     for (int k = 0; k < RPW / 2; ++k) {
         const int r = RPW * w + 2 * k + h;
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds(uint16_t* __restrict__ rank
 template <int P, bool WRITE_ALL = true>
 __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__ ranks, uint64_t stride,
                                                           const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                          uint64_t ntiles, uint16_t* __restrict__ out,
+                                                          TileSpan span, uint16_t* __restrict__ out,
                                                           uint64_t out_stride) {
     constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
     static_assert(OPS >= 1, "P >= 8");
@@ -223,13 +225,14 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
             lds_dma16(src, wbase + (uint32_t)(b * P * TV * 16 + RPI * k * TV * 16));
         }
     };
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    auto tile_of = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j); };
     // the order rows of all P blocks, once, then the first tile's loads
     for (int i = threadIdx.x; i < P * ALLRED_MAX_NODES / 16; i += kBlock)
         reinterpret_cast<uint4*>(ord_lds)[i] = reinterpret_cast<const uint4*>(order)[i];
     __syncthreads();
-    if (mine > 0) issue(blockIdx.x, 0);
+    if (mine > 0) issue(tile_of(0), 0);
+    TileBlock blk = tile_span_first(span, blockIdx.x);   // tile 0's block, then carried (tile_span.hpp)
     // The tile loop.  A workgroup has one tile's loads in flight while it reduces, so what a tile
     // costs between their arrival and the next tile's issue shows in the pass's time: the
     // hierarchical partial (one_block: block_vec == 0, tree 0 to out + v) gets a loop of its own
@@ -237,13 +240,14 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
     // takes order row and destination from the tile's block.
     auto tiles = [&](auto one_block) {
         for (int j = 0; j < mine; ++j) {
-            const uint64_t v0 = (blockIdx.x + (uint64_t)j * G) * TV;
-            const uint64_t b = one_block() ? 0 : (block_vec ? v0 / block_vec : 0);
+            const uint64_t v0 = tile_of(j) * TV;
+            const uint64_t b = one_block() ? 0 : blk.block;
+            if (!one_block()) tile_span_next(span, blk);
             if (WRITE_ALL) wait_tile<OPS, 1>(j < 1 ? j : 1);
             else if (j > 0 && w == 0) wait_vm<1>();   // tile j-1's result store may stay in flight
             else wait_vm<0>();
             lds_barrier();
-            if (j + 1 < mine) issue(blockIdx.x + (uint64_t)(j + 1) * G, (j + 1) & 1);
+            if (j + 1 < mine) issue(tile_of(j + 1), (j + 1) & 1);
             const uint4* tile = buf[j & 1];
             const uint4 pw = tree_wave_part<TV, LPL>(tile, ord_lds + b * ALLRED_MAX_NODES + RPW * w + LPL * q, c);
             if (q == 0) part[w * TV + c] = pw;
@@ -278,14 +282,18 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
 // L4 S1 | ..., so after tile j's loads come tile j+1's loads and the stores of
 // tiles j-2 and j-3.  The 4 KiB tree order table's load goes out first, then
 // the first two tiles' loads, and only the table's load is waited for before
-// it is staged into LDS.  Measured arms (the table first, an LDS-counter
-// barrier, 2 / 8 waves, 1 KiB rows, other interleave orders) and their
-// numbers: DESIGN.md §4, tools/ubench/fused_ab.hip.
+// it is staged into LDS.  Nothing stands between kernel entry and those loads
+// but one wait for the arguments: the tile index arithmetic is the host's
+// (TileSpan, tile_span.hpp — no division here; entry to first load 24 ns
+// against 275 ns with `mine` divided on the device), the block of a tile is
+// carried from iteration to iteration, and a lane's eight row addresses are
+// made once.  Measured arms (the table first, an LDS-counter barrier, 2 / 8
+// waves, 1 KiB rows, other interleave orders, the divisions on the device)
+// and their numbers: DESIGN.md §4, tools/ubench/fused_ab.hip.
 // ---------------------------------------------------------------------------
 template <int P>
 __global__ __launch_bounds__(kBlock) void k_tree_lds_lag(uint16_t* __restrict__ ranks, uint64_t stride,
-                                                         const uint8_t* __restrict__ order, uint64_t block_vec,
-                                                         uint64_t t0, uint64_t ntiles) {
+                                                         const uint8_t* __restrict__ order, TileSpan span) {
     constexpr int NW = 4, TV = 32, RPI = 2, RPW = P / NW, OPS = RPW / RPI, LPL = OPS;
     static_assert(OPS >= 1 && 3 * OPS <= 63, "vmcnt is 6 bits");
     __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
@@ -295,25 +303,46 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_lag(uint16_t* __restrict__ 
     const int c = lane % TV, q = lane / TV;
     const uint32_t wbase = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
-    auto row = [&](int k) { return ranks + (uint64_t)(RPW * w + RPI * k + q) * stride; };
-    auto issue = [&](uint64_t t, int b) {
-#pragma unroll
-        for (int k = 0; k < OPS; ++k)
-            lds_dma16(reinterpret_cast<const uint4*>(row(k)) + t * TV + c,
-                      wbase + (uint32_t)(b * P * TV * 16 + RPI * k * TV * 16));
-    };
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
-    auto tile_of = [&](int j) { return t0 + blockIdx.x + (uint64_t)j * G; };   // tiles t0 .. t0 + ntiles - 1
     // the 4 KiB order table (16 bytes per thread) is loaded ahead of the first two tiles
     // and waited for exactly, so tile 0's tree waits for tile 0 only, not for tile 1 too
     // (a compiler-issued load would be followed by vmcnt(0): it cannot see the LDS-DMA ops)
     static_assert(P * ALLRED_MAX_NODES == 16 * 64 * NW, "one 16-byte load per thread");
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
     u32x4 ov;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ov) : "v"(reinterpret_cast<const uint4*>(order) + threadIdx.x) : "memory");
-    if (mine > 0) issue(tile_of(0), 0);
-    if (mine > 1) issue(tile_of(1), 1);
-    if (mine > 1) wait_vm<2 * OPS>(); else if (mine > 0) wait_vm<OPS>(); else wait_vm<0>();
+    // ("+s" of ranks and stride: every argument is fetched before the one wait ahead of this
+    // load, and the row addresses below are made after the load is out, not before it)
+    asm volatile("global_load_dwordx4 %0, %3, off"
+                 : "=v"(ov), "+s"(stride), "+s"(ranks)
+                 : "v"(reinterpret_cast<const uint4*>(order) + threadIdx.x)
+                 : "memory");
+    if (mine == 0) {   // the whole workgroup: a grid wider than the tile range (no launcher makes one)
+        wait_vm<0>();
+        return;
+    }
+    auto tile_at = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j) * TV; };   // in vectors
+    // This lane's column of its OPS rank rows, made once (16 VGPRs): every load and store
+    // address of the pass is one of these plus the tile's wave-uniform offset.  Row k + 1 is
+    // row k plus RPI strides, and tile 0's load of a row goes out as soon as the row is known.
+    global_u32x4* rowp[OPS];
+    auto load = [&](int k, uint64_t tv, uint32_t lds) { lds_dma16((const void*)(rowp[k] + tv), lds); };
+    {
+        const uint64_t t = tile_at(0), step = RPI * stride / 8;   // stride % 8 == 0 (launcher)
+        rowp[0] = (global_u32x4*)(ranks + (uint64_t)(RPW * w + q) * stride) + c;
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            asm volatile("" : "+v"(rowp[k]));   // kept in registers, not recomputed per use
+            load(k, t, wbase + (uint32_t)(RPI * k * TV * 16));
+            if (k + 1 < OPS) rowp[k + 1] = rowp[k] + step;
+        }
+    }
+    if (mine > 1) {
+        const uint64_t t = tile_at(1);
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) load(k, t, wbase + (uint32_t)(P * TV * 16 + RPI * k * TV * 16));
+    }
+    // the block of tile 0 (first needed at its tree) while the loads are in flight; then carried
+    TileBlock blk = tile_span_first(span, blockIdx.x);
+    if (mine > 1) wait_vm<2 * OPS>(); else wait_vm<OPS>();
     asm volatile("" : "+v"(ov));   // no use of ov may move above the wait
     reinterpret_cast<u32x4*>(ord_lds)[threadIdx.x] = ov;
     lds_barrier();
@@ -323,27 +352,25 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_lag(uint16_t* __restrict__ 
         wait_any((j >= 3 ? 1 : 0) + (j + 1 < mine ? OPS : 0) + (j >= 2 ? OPS : 0));
         lds_barrier();   // every wave's rows of tile j are in LDS
         const uint4* tile = buf[j & 1];
-        const uint64_t t = tile_of(j), v0 = t * TV;
-        const uint8_t* ord = ord_lds + (block_vec ? v0 / block_vec : 0) * ALLRED_MAX_NODES + RPW * w + LPL * q;
+        const uint8_t* ord = ord_lds + blk.block * ALLRED_MAX_NODES + RPW * w + LPL * q;
+        tile_span_next(span, blk);
         const uint4 pw = tree_wave_part<TV, LPL>(tile, ord, c);
         if (q == 0) part[j & 1][w * TV + c] = pw;
         lds_barrier();   // every wave has read tile j out of buf[j & 1]; the partials are in
         {   // tile j+2's loads and tile j-1's stores, interleaved op by op
-            const uint64_t tl = tile_of(j + 2), ts = tile_of(j - 1);
+            const uint64_t tl = tile_at(j + 2), ts = tile_at(j - 1);
             const uint32_t bl = wbase + (uint32_t)((j & 1) * P * TV * 16);
 #pragma unroll
             for (int k = 0; k < OPS; ++k) {
-                if (j + 2 < mine)
-                    lds_dma16(reinterpret_cast<const uint4*>(row(k)) + tl * TV + c, bl + (uint32_t)(RPI * k * TV * 16));
-                if (j >= 1) st_nt(reinterpret_cast<uint4*>(row(k)) + ts * TV + c, prev);
+                if (j + 2 < mine) load(k, tl, bl + (uint32_t)(RPI * k * TV * 16));
+                if (j >= 1) st_nt(rowp[k] + ts, prev);
             }
         }
         prev = tree_join4<TV>(part[j & 1], c);
     }
-    if (mine > 0) {
+    const uint64_t tlast = tile_at(mine - 1);
 #pragma unroll
-        for (int k = 0; k < OPS; ++k) st_nt(reinterpret_cast<uint4*>(row(k)) + tile_of(mine - 1) * TV + c, prev);
-    }
+    for (int k = 0; k < OPS; ++k) st_nt(rowp[k] + tlast, prev);
 }
 
 // ---------------------------------------------------------------------------
@@ -370,8 +397,7 @@ template <int LAG, bool BAL>
 __global__ __launch_bounds__(kBlock) void k_tree_bcast_x(uint16_t* __restrict__ cur, uint16_t* __restrict__ prev,
                                                          uint64_t stride, const uint8_t* __restrict__ order,
                                                          uint16_t* __restrict__ cur_partial,
-                                                         const uint16_t* __restrict__ prev_result, uint64_t t0,
-                                                         uint64_t ntiles) {
+                                                         const uint16_t* __restrict__ prev_result, TileSpan span) {
     constexpr int P = 64, NW = 4, TV = 32, RPI = 2, RPW = P / NW, OPS = RPW / RPI, LPL = OPS;
     static_assert(2 * OPS + 3 <= 63, "vmcnt is 6 bits");
     static_assert(LAG == 0 || LAG == 1, "lag of the row stores: 0 or 1 iteration");
@@ -389,9 +415,8 @@ __global__ __launch_bounds__(kBlock) void k_tree_bcast_x(uint16_t* __restrict__ 
         (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&res_lds[0][0]);
     auto crow = [&](int k) { return cur + (uint64_t)(RPW * w + RPI * k + q) * stride; };
     auto prow = [&](int k) { return prev + (uint64_t)(RPW * w + RPI * k + q) * stride; };
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
-    auto tile_of = [&](int j) { return t0 + blockIdx.x + (uint64_t)j * G; };
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    auto tile_of = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j); };
     const uint32_t rbase_w = __builtin_amdgcn_readfirstlane(rbase + (uint32_t)(w * 128));   // BAL: this wave's 8 columns
     auto issue_res = [&](uint64_t t, int slot) {   // bucket i's result tile t into res_lds[slot]
         if (BAL) {
@@ -593,7 +618,7 @@ __global__ __launch_bounds__(kBlock) void k_butterfly_lds64(uint16_t* __restrict
 template <int EX>   // 0 or 4
 __global__ __launch_bounds__(kBlock) void k_butterfly_lds64_pipe(uint16_t* __restrict__ ranks, uint64_t stride,
                                                                  const int16_t* __restrict__ partner, int steps,
-                                                                 uint64_t ntiles, const uint8_t* __restrict__ dag) {
+                                                                 TileSpan span, const uint8_t* __restrict__ dag) {
     constexpr int TV = 32, OPS = 8;
     __shared__ __attribute__((aligned(16))) uint4 buf[2][64 * TV];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -609,8 +634,8 @@ __global__ __launch_bounds__(kBlock) void k_butterfly_lds64_pipe(uint16_t* __res
             lds_dma16(src, wbase + (uint32_t)(b * 64 * TV * 16 + 2 * k * TV * 16));
         }
     };
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    auto tile_of = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j); };
     // partner table first, then the first tile's loads (the other order
     // measured slower: 24.0-24.3 vs 23.6-23.9 us at 640 kB)
     int src_lane[ALLRED_MAX_STEPS];
@@ -633,13 +658,13 @@ __global__ __launch_bounds__(kBlock) void k_butterfly_lds64_pipe(uint16_t* __res
         for (int k = 0; k < OPS; ++k) fin[k] = (int)(fw[k >> 1] >> (8 * (2 * (k & 1) + h))) & 255;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (mine > 0) issue(blockIdx.x, 0);
+    if (mine > 0) issue(tile_of(0), 0);
     for (int j = 0; j < mine; ++j) {
         wait_tile<OPS, 1>(j < 1 ? j : 1);
         lds_barrier();
-        if (j + 1 < mine) issue(blockIdx.x + (uint64_t)(j + 1) * G, (j + 1) & 1);
+        if (j + 1 < mine) issue(tile_of(j + 1), (j + 1) & 1);
         uint4* tile = buf[j & 1];
-        const uint64_t v0 = (blockIdx.x + (uint64_t)j * G) * TV;
+        const uint64_t v0 = tile_of(j) * TV;
         if constexpr (EX == 0) {
             uint4 val[8];
 #pragma unroll
@@ -720,7 +745,7 @@ __device__ __forceinline__ void lo_dag_eval(float* v, std::integer_sequence<int,
 
 template <class D>
 __global__ __launch_bounds__(kBlock) void k_lo_dag_reg(uint16_t* __restrict__ ranks, uint64_t stride,
-                                                       uint64_t t0, uint64_t ntiles) {
+                                                       TileSpan span) {
     constexpr int P = D::P, F = D::F, NW = 4, TV = 32, RPI = 2, RPW = P / NW, OPS = RPW / RPI;
     static_assert(OPS >= 1 && 3 * OPS <= 63, "vmcnt is 6 bits");
     static_assert(NW * 64 == 256 && TV * 8 == 256, "one element of the 256-element tile per thread");
@@ -743,9 +768,8 @@ __global__ __launch_bounds__(kBlock) void k_lo_dag_reg(uint16_t* __restrict__ ra
                 if (w == ww && q == qq) f = D::fin[RPW * ww + RPI * k + qq];
         fsel[k] = f;
     }
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
-    auto tile_of = [&](int j) { return t0 + blockIdx.x + (uint64_t)j * G; };
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    auto tile_of = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j); };
     auto issue = [&](uint64_t t, int b) {
 #pragma unroll
         for (int k = 0; k < OPS; ++k)
@@ -853,7 +877,7 @@ __global__ __launch_bounds__(128) void k_mem_lds(uint16_t* __restrict__ ranks, u
 // ---------------------------------------------------------------------------
 template <bool ACC16 = false>
 __global__ __launch_bounds__(kBlock) void k_mem_lds_lag(uint16_t* __restrict__ ranks, uint64_t stride,
-                                                        uint64_t block_vec, uint64_t t0, uint64_t ntiles) {
+                                                        TileSpan span) {
     constexpr int P = 64, TV = 32, RPW = 16, OPS = 8;
     __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
     __shared__ __attribute__((aligned(16))) uint4 resb[2][TV];
@@ -876,19 +900,19 @@ __global__ __launch_bounds__(kBlock) void k_mem_lds_lag(uint16_t* __restrict__ r
             st_nt(reinterpret_cast<uint4*>(ranks + (uint64_t)r * stride) + t * TV + c, res);
         }
     };
-    const uint64_t G = gridDim.x;
-    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
-    auto tile_of = [&](int j) { return t0 + blockIdx.x + (uint64_t)j * G; };
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    auto tile_of = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j); };
     if (mine > 0) issue(tile_of(0), 0);
     if (mine > 1) issue(tile_of(1), 1);
+    TileBlock blk = tile_span_first(span, blockIdx.x);   // tile 0's owner block, then carried (tile_span.hpp)
     uint4 prev = make_uint4(0, 0, 0, 0);
     const int e = threadIdx.x;   // element of the tile (0..255)
     for (int j = 0; j < mine; ++j) {
         // after L(j): the last op of S(j-3) (interleaved with L(j)), L(j+1), S(j-2)
         wait_any((j >= 3 ? 1 : 0) + (j + 1 < mine ? OPS : 0) + (j >= 2 ? OPS : 0));
         lds_barrier();
-        const uint64_t t = tile_of(j);
-        const int own = (int)(t * TV / block_vec);
+        const int own = (int)blk.block;
+        tile_span_next(span, blk);
         uint16_t* t16 = reinterpret_cast<uint16_t*>(buf[j & 1]);
         // the owner's element seeds the sum and is replaced by -0.0 (x + -0.0 == x
         // for every x, -0.0 included), so the 64-rank loop has no branch and its
@@ -1609,14 +1633,19 @@ int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, c
     // per CU), as the fused pass.  (The early-release / two-tiles-ahead forms measured slower
     // on this read-only stream: 10.4 / 9.9 vs 9.6 us, profiles/r01_partial_ab.txt.)
     if (!WRITE_ALL && whole_tiles && form != 1 && form != 2 && ((total == 64 && tiles >= 1024) || form == 3)) {
+        const unsigned grid = persistent_grid(tiles, 512);
+        TileSpan span;
+        if (!tile_span_make(&span, 0, tiles, grid, block_vec / 32)) return ALLRED_ERR_ARG;
         found = for_ranks<8, 64>(total, [&](auto p) {
-            hipLaunchKernelGGL((k_tree_lds_pipe<p(), false>), dim3(persistent_grid(tiles, 512)), dim3(kBlock), 0, st,
-                               ranks, stride, order, block_vec, tiles, out, out_stride);
+            hipLaunchKernelGGL((k_tree_lds_pipe<p(), false>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order,
+                               block_vec, span, out, out_stride);
         });
     } else if (whole_tiles && form != 1) {   // one tile per workgroup, staged in LDS
+        TileSpan span;
+        if (!tile_span_make(&span, 0, tiles, tiles, block_vec / 32)) return ALLRED_ERR_ARG;
         found = for_ranks<8, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree_lds<p(), WRITE_ALL>), dim3((unsigned)tiles), dim3(kBlock), 0, st, ranks, stride,
-                               order, block_vec, out, out_stride);
+                               order, block_vec, span, out, out_stride);
         });
     } else {   // the register form: fewer than 8 ranks, and buckets that are not whole tiles
         const int lanes = total >= 8 ? total / 8 : 1;
@@ -1753,10 +1782,12 @@ int launch_tree_fused(uint16_t* ranks, uint64_t stride, size_t n, int total, con
     // per CU (14.2-14.3 us vs 15.3 for k_tree_lds_pipe and 16.2 for one tile
     // per workgroup)
     if (whole_tiles && !host_memory && total == 64 && form == 0 && tiles >= 1024) {
+        if (tiles > kTileSpanMaxTiles) return ALLRED_ERR_ARG;   // 32-bit tile indices (tile_span.hpp)
         for_each_chunk(tiles, [&](uint64_t a, uint64_t b) {
             const unsigned grid = persistent_grid(b - a, 512);
-            hipLaunchKernelGGL((k_tree_lds_lag<64>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv, a,
-                               b - a);
+            TileSpan span;
+            tile_span_make(&span, a, b - a, grid, bv / 32);
+            hipLaunchKernelGGL((k_tree_lds_lag<64>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, span);
             note_launch(reinterpret_cast<const void*>(&k_tree_lds_lag<64>), "k_tree_lds_lag<64>", grid, kBlock);
         });
         return last_error();
@@ -1765,9 +1796,11 @@ int launch_tree_fused(uint16_t* ranks, uint64_t stride, size_t n, int total, con
     // directions busy, tools/pcie_probe.py), or forced persistent form
     if (whole_tiles && (host_memory || form == 3)) {
         const unsigned grid = persistent_grid(tiles, host_memory ? 32 : 512);
+        TileSpan span;
+        if (!tile_span_make(&span, 0, tiles, grid, bv / 32)) return ALLRED_ERR_ARG;
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree_lds_pipe<p(), true>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv,
-                               tiles, nullptr, (uint64_t)0);
+                               span, nullptr, (uint64_t)0);
         });
         if (!found) return ALLRED_ERR_UNSUPPORTED;
         return last_error();
@@ -1778,12 +1811,15 @@ int launch_tree_fused(uint16_t* ranks, uint64_t stride, size_t n, int total, con
 int launch_lo_dag_reg(uint16_t* ranks, uint64_t stride, size_t n, int algo, int side, int total, void* stream) {
     if (n % 256 || stride % 8 || !aligned16(ranks)) return ALLRED_ERR_UNSUPPORTED;
     const uint64_t tiles = n / 256;
+    if (tiles > kTileSpanMaxTiles) return ALLRED_ERR_ARG;   // 32-bit tile indices (tile_span.hpp)
     hipStream_t st = (hipStream_t)stream;
 #define TSA_X(D, A, S, T)                                                                             \
     if (algo == (A) && total == (T) && ((A) == ALLRED_SWING_1D || side == (S))) {                      \
         for_each_chunk(tiles, [&](uint64_t a, uint64_t b) {                                           \
-            hipLaunchKernelGGL(k_lo_dag_reg<D>, dim3(persistent_grid(b - a, 512)), dim3(kBlock), 0, st, \
-                               ranks, stride, a, b - a);                                              \
+            const unsigned grid = persistent_grid(b - a, 512);                                        \
+            TileSpan span;                                                                            \
+            tile_span_make(&span, a, b - a, grid, 0);                                                 \
+            hipLaunchKernelGGL(k_lo_dag_reg<D>, dim3(grid), dim3(kBlock), 0, st, ranks, stride, span); \
         });                                                                                           \
         return last_error();                                                                          \
     }
@@ -1808,12 +1844,14 @@ int launch_butterfly(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
     if (total == 64 && nv % 32 == 0 && nv >= 32 &&
         (dag_pipe || (tiles >= 256 && (form == 3 || (tiles >= 1024 && form != 2))))) {
         const dim3 grid(persistent_grid(tiles, 512));
+        TileSpan span;
+        if (!tile_span_make(&span, 0, tiles, grid.x, 0)) return ALLRED_ERR_ARG;
         if (dag)
             hipLaunchKernelGGL(k_butterfly_lds64_pipe<4>, grid, dim3(kBlock), 0, st, ranks, stride, d_partner, steps,
-                               tiles, dag);
+                               span, dag);
         else
             hipLaunchKernelGGL(k_butterfly_lds64_pipe<0>, grid, dim3(kBlock), 0, st, ranks, stride, d_partner, steps,
-                               tiles, nullptr);
+                               span, nullptr);
         return last_error();
     }
     if (total == 64 && nv % 32 == 0 && tiles >= 256) {  // >= 256 tiles: the LDS-staged form pays
@@ -1865,12 +1903,15 @@ int launch_tree_bcast_x(uint16_t* cur, uint16_t* prev, uint64_t stride, size_t n
         return ALLRED_ERR_ARG;
     // 64 ranks in whole 256-element tiles: one fused pass; else the two launches (same bits)
     if (total == 64 && n % 256 == 0) {
+        if (n / 256 > kTileSpanMaxTiles) return ALLRED_ERR_ARG;   // 32-bit tile indices (tile_span.hpp)
         hipStream_t st = (hipStream_t)stream;
         for_each_chunk(n / 256, [&](uint64_t a, uint64_t b) {
             const dim3 grid(persistent_grid(b - a, 512));
+            TileSpan span;
+            tile_span_make(&span, a, b - a, grid.x, 0);
             switch (tune(Tune::tree_bcast_lag) * 2 + tune(Tune::tree_bcast_bal)) {
 #define TSA_TBX(L, B) hipLaunchKernelGGL((k_tree_bcast_x<L, B>), grid, dim3(kBlock), 0, st, cur, prev, stride, order, \
-                                         cur_partial, prev_result, a, b - a)
+                                         cur_partial, prev_result, span)
                 case 0: TSA_TBX(0, false); break;
                 case 1: TSA_TBX(0, true); break;
                 case 2: TSA_TBX(1, false); break;
@@ -2044,9 +2085,12 @@ int mem_fused_impl(uint16_t* ranks, uint64_t stride, uint64_t nv, int total, hip
     const uint64_t bv = nv / total, tiles = nv / 32;
     if (bv % 32 == 0 && total == 64 && tiles >= 1024 && fused_form() == 0) {
         // persistent, stores one iteration late (k_tree_lds_lag's schedule)
+        if (tiles > kTileSpanMaxTiles) return ALLRED_ERR_ARG;   // 32-bit tile indices (tile_span.hpp)
         for_each_chunk(tiles, [&](uint64_t a, uint64_t b) {
-            hipLaunchKernelGGL((k_mem_lds_lag<ACC16>), dim3(persistent_grid(b - a, 512)), dim3(kBlock), 0, st, ranks,
-                               stride, bv, a, b - a);
+            const unsigned grid = persistent_grid(b - a, 512);
+            TileSpan span;
+            tile_span_make(&span, a, b - a, grid, bv / 32);
+            hipLaunchKernelGGL((k_mem_lds_lag<ACC16>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, span);
         });
         return last_error();
     }

@@ -2,7 +2,10 @@
 // 327,680 bf16, stride n + 64) in ONE process, interleaved rounds, 32 rotating
 // bucket sets: k_tree_lds_pipe_ab<64,1,32,true,true> (the round-1 product),
 // and the k_tree_lds_lag_ab<64,32,VAR> arms — the A/B arms of round 1, kept
-// here (the product library carries only VAR 7 as k_tree_lds_lag<64>).  First checks that all forms give identical bits on random
+// here (the product library carries VAR 7 with its tile index arithmetic from
+// tile_span.hpp as k_tree_lds_lag<64>; k_tree_lds_lag_div<64> below is that
+// kernel as it was with the divisions on the device, and `fused_ab REPS pairs N`
+// times the two in interleaved pairs and runs their stamped forms).  First checks that all forms give identical bits on random
 // bf16 with a random per-block tree order table.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I../../include \
 //         -I../../tenstorrentallreduce_amd/csrc fused_ab.hip -o fused_ab -L../../tenstorrentallreduce_amd/lib -lallred
@@ -256,6 +259,188 @@ __global__ __launch_bounds__(64 * NW) void k_tree_lds_lag_ab(uint16_t* __restric
     }
     if (mine > 0) store(tile_of(mine - 1), prev);
 }
+
+// ---------------------------------------------------------------------------
+// A stamp: the 100 MHz s_memrealtime clock and the shader clock (s_memtime), read
+// in one statement with their wait.  STAMPED forms only, never the product kernel:
+// a workgroup's four stamps (entry; before its first load; after its last prologue
+// load is issued; tile 0 landed) leave through a buffer of their own, by ordinary
+// vector stores of thread 0 after the last tile's stores.
+// ---------------------------------------------------------------------------
+struct Stamp {
+    uint64_t rt, ct;
+};
+__device__ __forceinline__ Stamp stamp_now() {
+    Stamp s;
+    asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=&s"(s.rt), "=&s"(s.ct)::"memory");
+    return s;
+}
+constexpr int kStamps = 4;
+__device__ __forceinline__ void stamps_out(uint64_t* out, const Stamp (&s)[kStamps]) {
+    if (out && threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kStamps; ++i) {
+            out[(blockIdx.x * kStamps + i) * 2 + 0] = s[i].rt;
+            out[(blockIdx.x * kStamps + i) * 2 + 1] = s[i].ct;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_tree_lds_lag_div: the product kernel as it was before tile_span.hpp — `mine`
+// by a 64-bit division ahead of the first load, the block of every tile by a
+// 64-bit division between "tile j landed" and its tree, every row address
+// recomputed per load and store.  Kept as the parent arm of the tile-span A/B
+// (profiles/fused_tilespan_ab.txt).  STAMP: the stamped form (timing of its
+// segments only; its run time is not the kernel's).
+// ---------------------------------------------------------------------------
+template <int P, bool STAMP = false>
+__global__ __launch_bounds__(kBlock) void k_tree_lds_lag_div(uint16_t* __restrict__ ranks, uint64_t stride,
+                                                             const uint8_t* __restrict__ order, uint64_t block_vec,
+                                                             uint64_t t0, uint64_t ntiles, uint64_t* stamps) {
+    constexpr int NW = 4, TV = 32, RPI = 2, RPW = P / NW, OPS = RPW / RPI, LPL = OPS;
+    static_assert(OPS >= 1 && 3 * OPS <= 63, "vmcnt is 6 bits");
+    Stamp ts4[kStamps] = {};
+    if (STAMP) ts4[0] = stamp_now();
+    __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
+    __shared__ __attribute__((aligned(16))) uint4 part[2][NW * TV];
+    __shared__ __attribute__((aligned(16))) uint8_t ord_lds[P * ALLRED_MAX_NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    const uint32_t wbase = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
+    auto row = [&](int k) { return ranks + (uint64_t)(RPW * w + RPI * k + q) * stride; };
+    auto issue = [&](uint64_t t, int b) {
+#pragma unroll
+        for (int k = 0; k < OPS; ++k)
+            lds_dma16(reinterpret_cast<const uint4*>(row(k)) + t * TV + c,
+                      wbase + (uint32_t)(b * P * TV * 16 + RPI * k * TV * 16));
+    };
+    const uint64_t G = gridDim.x;
+    const int mine = blockIdx.x < ntiles ? (int)((ntiles - 1 - blockIdx.x) / G + 1) : 0;
+    auto tile_of = [&](int j) { return t0 + blockIdx.x + (uint64_t)j * G; };   // tiles t0 .. t0 + ntiles - 1
+    static_assert(P * ALLRED_MAX_NODES == 16 * 64 * NW, "one 16-byte load per thread");
+    if (STAMP) {
+        asm volatile("" ::"s"(mine));   // the division is done before this stamp
+        ts4[1] = stamp_now();
+    }
+    u32x4 ov;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ov) : "v"(reinterpret_cast<const uint4*>(order) + threadIdx.x) : "memory");
+    if (mine > 0) issue(tile_of(0), 0);
+    if (mine > 1) issue(tile_of(1), 1);
+    if (STAMP) ts4[2] = stamp_now();
+    if (mine > 1) wait_vm<2 * OPS>(); else if (mine > 0) wait_vm<OPS>(); else wait_vm<0>();
+    asm volatile("" : "+v"(ov));   // no use of ov may move above the wait
+    reinterpret_cast<u32x4*>(ord_lds)[threadIdx.x] = ov;
+    lds_barrier();
+    uint4 prev = make_uint4(0, 0, 0, 0);
+    for (int j = 0; j < mine; ++j) {
+        wait_any((j >= 3 ? 1 : 0) + (j + 1 < mine ? OPS : 0) + (j >= 2 ? OPS : 0));
+        lds_barrier();   // every wave's rows of tile j are in LDS
+        if (STAMP && j == 0) ts4[3] = stamp_now();
+        const uint4* tile = buf[j & 1];
+        const uint64_t t = tile_of(j), v0 = t * TV;
+        const uint8_t* ord = ord_lds + (block_vec ? v0 / block_vec : 0) * ALLRED_MAX_NODES + RPW * w + LPL * q;
+        const uint4 pw = tree_wave_part<TV, LPL>(tile, ord, c);
+        if (q == 0) part[j & 1][w * TV + c] = pw;
+        lds_barrier();   // every wave has read tile j out of buf[j & 1]; the partials are in
+        {   // tile j+2's loads and tile j-1's stores, interleaved op by op
+            const uint64_t tl = tile_of(j + 2), ts = tile_of(j - 1);
+            const uint32_t bl = wbase + (uint32_t)((j & 1) * P * TV * 16);
+#pragma unroll
+            for (int k = 0; k < OPS; ++k) {
+                if (j + 2 < mine)
+                    lds_dma16(reinterpret_cast<const uint4*>(row(k)) + tl * TV + c, bl + (uint32_t)(RPI * k * TV * 16));
+                if (j >= 1) st_nt(reinterpret_cast<uint4*>(row(k)) + ts * TV + c, prev);
+            }
+        }
+        prev = tree_join4<TV>(part[j & 1], c);
+    }
+    if (mine > 0) {
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) st_nt(reinterpret_cast<uint4*>(row(k)) + tile_of(mine - 1) * TV + c, prev);
+    }
+    if (STAMP) stamps_out(stamps, ts4);
+}
+
+// the product k_tree_lds_lag<64> (kernels.hip, tile_span.hpp) with the same four stamps
+template <int P>
+__global__ __launch_bounds__(kBlock) void k_tree_lds_lag_span_stamped(uint16_t* __restrict__ ranks, uint64_t stride,
+                                                                      const uint8_t* __restrict__ order, TileSpan span,
+                                                                      uint64_t* stamps) {
+    constexpr int NW = 4, TV = 32, RPI = 2, RPW = P / NW, OPS = RPW / RPI, LPL = OPS;
+    Stamp ts4[kStamps] = {};
+    ts4[0] = stamp_now();
+    __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
+    __shared__ __attribute__((aligned(16))) uint4 part[2][NW * TV];
+    __shared__ __attribute__((aligned(16))) uint8_t ord_lds[P * ALLRED_MAX_NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    const uint32_t wbase = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
+    const int mine = (int)tile_span_mine(span, blockIdx.x);
+    asm volatile("" ::"s"(mine));
+    ts4[1] = stamp_now();
+    u32x4 ov;
+    asm volatile("global_load_dwordx4 %0, %3, off"
+                 : "=v"(ov), "+s"(stride), "+s"(ranks)
+                 : "v"(reinterpret_cast<const uint4*>(order) + threadIdx.x)
+                 : "memory");
+    if (mine == 0) {
+        wait_vm<0>();
+        return;
+    }
+    auto tile_at = [&](int j) { return (uint64_t)tile_span_tile(span, blockIdx.x, (uint32_t)j) * TV; };
+    global_u32x4* rowp[OPS];
+    auto load = [&](int k, uint64_t tv, uint32_t lds) { lds_dma16((const void*)(rowp[k] + tv), lds); };
+    {
+        const uint64_t t = tile_at(0), step = RPI * stride / 8;
+        rowp[0] = (global_u32x4*)(ranks + (uint64_t)(RPW * w + q) * stride) + c;
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            asm volatile("" : "+v"(rowp[k]));
+            load(k, t, wbase + (uint32_t)(RPI * k * TV * 16));
+            if (k + 1 < OPS) rowp[k + 1] = rowp[k] + step;
+        }
+    }
+    if (mine > 1) {
+        const uint64_t t = tile_at(1);
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) load(k, t, wbase + (uint32_t)(P * TV * 16 + RPI * k * TV * 16));
+    }
+    ts4[2] = stamp_now();
+    TileBlock blk = tile_span_first(span, blockIdx.x);
+    if (mine > 1) wait_vm<2 * OPS>(); else wait_vm<OPS>();
+    asm volatile("" : "+v"(ov));
+    reinterpret_cast<u32x4*>(ord_lds)[threadIdx.x] = ov;
+    lds_barrier();
+    uint4 prev = make_uint4(0, 0, 0, 0);
+    for (int j = 0; j < mine; ++j) {
+        wait_any((j >= 3 ? 1 : 0) + (j + 1 < mine ? OPS : 0) + (j >= 2 ? OPS : 0));
+        lds_barrier();
+        if (j == 0) ts4[3] = stamp_now();
+        const uint4* tile = buf[j & 1];
+        const uint8_t* ord = ord_lds + blk.block * ALLRED_MAX_NODES + RPW * w + LPL * q;
+        tile_span_next(span, blk);
+        const uint4 pw = tree_wave_part<TV, LPL>(tile, ord, c);
+        if (q == 0) part[j & 1][w * TV + c] = pw;
+        lds_barrier();
+        {
+            const uint64_t tl = tile_at(j + 2), ts = tile_at(j - 1);
+            const uint32_t bl = wbase + (uint32_t)((j & 1) * P * TV * 16);
+#pragma unroll
+            for (int k = 0; k < OPS; ++k) {
+                if (j + 2 < mine) load(k, tl, bl + (uint32_t)(RPI * k * TV * 16));
+                if (j >= 1) st_nt(rowp[k] + ts, prev);
+            }
+        }
+        prev = tree_join4<TV>(part[j & 1], c);
+    }
+    const uint64_t tlast = tile_at(mine - 1);
+#pragma unroll
+    for (int k = 0; k < OPS; ++k) st_nt(rowp[k] + tlast, prev);
+    stamps_out(stamps, ts4);
+}
 }  // namespace
 }  // namespace tsa
 
@@ -299,9 +484,18 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(order, ord.data(), ord.size(), hipMemcpyHostToDevice));
     hipStream_t st;
     CK(hipStreamCreate(&st));
-    constexpr int NF = 13;
+    constexpr int NF = 15, F_DIV = 13, F_SPAN = 14;
+    TileSpan span;
+    if (!tile_span_make(&span, 0, tiles, grid, bv / 32)) return 1;
+    uint64_t* stamps;
+    CK(hipMalloc(&stamps, (size_t)grid * kStamps * 2 * sizeof(uint64_t)));
     auto run = [&](int form, uint16_t* r) {
-        if (form == 0)
+        if (form == F_DIV)   // the product before tile_span.hpp: 64-bit divisions, addresses per op
+            hipLaunchKernelGGL((k_tree_lds_lag_div<64>), dim3(grid), dim3(kBlock), 0, st, r, stride, order, bv,
+                               (uint64_t)0, (uint64_t)tiles, nullptr);
+        else if (form == F_SPAN)   // the product kernel of the library
+            hipLaunchKernelGGL((k_tree_lds_lag<64>), dim3(grid), dim3(kBlock), 0, st, r, stride, order, span);
+        else if (form == 0)
             hipLaunchKernelGGL((k_tree_lds_pipe_ab<64, 1, 32, true, true>), dim3(grid), dim3(kBlock), 0, st, r, stride,
                                order, bv, tiles, nullptr);
         else if (form == 1)
@@ -338,13 +532,20 @@ int main(int argc, char** argv) {
                              "k_tree_lds_lag<64,64,2> 1 KiB rows, grid 256", "k_tree_lds_lag<64,32,2,2> two waves",
                              "k_tree_lds_lag<64,32,2,8> eight waves", "k_tree_lds_lag<64,32,7> interleaved (product)",
                              "k_tree_lds_lag<64,32,8> interleaved S L", "k_tree_lds_lag<64,32,9> interleaved L L S S",
-                             "k_tree_lds_lag<64,16,7> 256-B rows, grid 512", "k_tree_lds_lag<64,16,7> 256-B rows, grid 1024"};
+                             "k_tree_lds_lag<64,16,7> 256-B rows, grid 512", "k_tree_lds_lag<64,16,7> 256-B rows, grid 1024",
+                             "k_tree_lds_lag_div<64> (parent: divisions on the device)",
+                             "k_tree_lds_lag<64> (product: tile_span)"};
+    // `fused_ab REPS pairs [N]`: only the parent arm and the product kernel, N interleaved pairs (default 7),
+    // then the stamped forms and the kernels' registers and residency
+    const bool pairs = argc > 2 && !std::strcmp(argv[2], "pairs");
+    const int npairs = argc > 3 ? std::atoi(argv[3]) : 7;
     // bits: every form on a copy of set 0
     const size_t bytes = (size_t)P * stride * 2;
     std::vector<uint16_t> ref(P * stride), got(P * stride);
     uint16_t* tmp;
     CK(hipMalloc(&tmp, bytes));
     for (int form = 0; form < NF; ++form) {
+        if (pairs && form && form != F_DIV && form != F_SPAN) continue;
         CK(hipMemcpy(tmp, sets[0], bytes, hipMemcpyDeviceToDevice));
         run(form, tmp);
         CK(hipStreamSynchronize(st));
@@ -359,19 +560,85 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    for (int round = 0; round < 3; ++round) {
-        for (int form = 0; form < NF; ++form) {
-            for (int i = 0; i < 20; ++i) run(form, sets[i % SETS]);
-            CK(hipEventRecord(e0, st));
-            for (int i = 0; i < REPS; ++i) run(form, sets[i % SETS]);
-            CK(hipEventRecord(e1, st));
-            CK(hipEventSynchronize(e1));
-            float ms;
-            CK(hipEventElapsedTime(&ms, e0, e1));
-            const double us = ms * 1e3 / REPS;
-            std::printf("{\"form\": \"%s\", \"round\": %d, \"us\": %.3f, \"hbm_frac\": %.4f}\n", names[form], round, us,
-                        2.0 * P * n * 2 / (us * 1e-6) / 8e12);
+    auto time_form = [&](int form, int round) {
+        for (int i = 0; i < 20; ++i) run(form, sets[i % SETS]);
+        CK(hipEventRecord(e0, st));
+        for (int i = 0; i < REPS; ++i) run(form, sets[i % SETS]);
+        CK(hipEventRecord(e1, st));
+        CK(hipEventSynchronize(e1));
+        float ms;
+        CK(hipEventElapsedTime(&ms, e0, e1));
+        const double us = ms * 1e3 / REPS;
+        std::printf("{\"form\": \"%s\", \"round\": %d, \"us\": %.3f, \"hbm_frac\": %.4f}\n", names[form], round, us,
+                    2.0 * P * n * 2 / (us * 1e-6) / 8e12);
+        return us;
+    };
+    if (!pairs) {
+        for (int round = 0; round < 3; ++round)
+            for (int form = 0; form < NF; ++form) time_form(form, round);
+        return 0;
+    }
+    // the pairs and their rule: the product faster in every pair, and the median gain at least twice the
+    // parent arm's own max - min over the pairs
+    // (three untimed pairs first: the first rounds of a process run slower in both arms while the clocks
+    // settle — 14.61 / 14.51 us, then 14.20-14.26 — and that drift is not the parent arm's spread)
+    for (int r = 0; r < 3; ++r)
+        for (int form : {F_DIV, F_SPAN})
+            for (int i = 0; i < 20 + REPS; ++i) run(form, sets[i % SETS]);
+    std::vector<double> a(npairs), b(npairs), gain(npairs);
+    for (int r = 0; r < npairs; ++r) {
+        a[r] = time_form(F_DIV, r);
+        b[r] = time_form(F_SPAN, r);
+        gain[r] = a[r] - b[r];
+    }
+    const bool every = std::all_of(gain.begin(), gain.end(), [](double g) { return g > 0; });
+    const double spread = *std::max_element(a.begin(), a.end()) - *std::min_element(a.begin(), a.end());
+    std::vector<double> gs = gain;
+    std::sort(gs.begin(), gs.end());
+    const double med = npairs % 2 ? gs[npairs / 2] : 0.5 * (gs[npairs / 2 - 1] + gs[npairs / 2]);
+    std::printf("{\"pairs\": %d, \"faster_in_every_pair\": %s, \"median_gain_us\": %.3f, \"parent_max_minus_min_us\": %.3f, "
+                "\"rule_holds\": %s}\n", npairs, every ? "true" : "false", med, spread,
+                every && med >= 2 * spread ? "true" : "false");
+    // the stamped forms: per workgroup, ticks of the 100 MHz clock (10 ns) and shader clocks from entry
+    const char* snames[2] = {"k_tree_lds_lag_div<64> stamped", "k_tree_lds_lag<64> (tile_span) stamped"};
+    std::vector<uint64_t> hs((size_t)grid * kStamps * 2);
+    for (int f = 0; f < 2; ++f) {
+        for (int rep = 0; rep < 5; ++rep) {   // the last of five launches is read
+            if (f == 0)
+                hipLaunchKernelGGL((k_tree_lds_lag_div<64, true>), dim3(grid), dim3(kBlock), 0, st, sets[rep], stride, order,
+                                   bv, (uint64_t)0, (uint64_t)tiles, stamps);
+            else
+                hipLaunchKernelGGL((k_tree_lds_lag_span_stamped<64>), dim3(grid), dim3(kBlock), 0, st, sets[rep], stride,
+                                   order, span, stamps);
         }
+        CK(hipStreamSynchronize(st));
+        CK(hipMemcpy(hs.data(), stamps, hs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        const char* seg[3] = {"entry_to_first_issue", "entry_to_last_prologue_load", "entry_to_tile0_landed"};
+        for (int i = 1; i < kStamps; ++i) {
+            std::vector<double> rt(grid), ct(grid);
+            for (unsigned g2 = 0; g2 < grid; ++g2) {
+                rt[g2] = 10.0 * (double)(hs[(g2 * kStamps + i) * 2] - hs[(g2 * kStamps) * 2]);
+                ct[g2] = (double)(hs[(g2 * kStamps + i) * 2 + 1] - hs[(g2 * kStamps) * 2 + 1]);
+            }
+            const double rmean = std::accumulate(rt.begin(), rt.end(), 0.0) / grid;
+            const double cmean = std::accumulate(ct.begin(), ct.end(), 0.0) / grid;
+            std::sort(rt.begin(), rt.end());
+            std::sort(ct.begin(), ct.end());
+            std::printf("{\"stamped\": \"%s\", \"segment\": \"%s\", \"ns_mean\": %.1f, \"ns_median\": %.0f, \"ns_max\": %.0f, "
+                        "\"clk_mean\": %.0f, \"clk_median\": %.0f}\n", snames[f], seg[i - 1], rmean, rt[grid / 2], rt[grid - 1],
+                        cmean, ct[grid / 2]);
+        }
+    }
+    // registers and residency of the two timed kernels
+    const void* fn[2] = {reinterpret_cast<const void*>(&k_tree_lds_lag_div<64, false>),
+                         reinterpret_cast<const void*>(&k_tree_lds_lag<64>)};
+    for (int f = 0; f < 2; ++f) {
+        hipFuncAttributes fa;
+        int nb = 0;
+        CK(hipFuncGetAttributes(&fa, fn[f]));
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn[f], kBlock, 0));
+        std::printf("{\"kernel\": \"%s\", \"vgprs\": %d, \"lds_bytes\": %zu, \"workgroups_per_cu\": %d}\n",
+                    names[f ? F_SPAN : F_DIV], fa.numRegs, (size_t)fa.sharedSizeBytes, nb);
     }
     return 0;
 }
