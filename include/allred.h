@@ -32,7 +32,9 @@ extern "C" {
  * no existing struct layout, signature or behaviour changes, so the version stays.
  * Still ABI 7: allred_plan_reduce_scatter / allred_plan_all_gather and allred_dist_reduce_scatter /
  * allred_dist_all_gather (+ their _host twins) are additions too — the two halves of the BO
- * allreduce as calls of their own, on the existing plans, descs and communicators. */
+ * allreduce as calls of their own, on the existing plans, descs and communicators.
+ * Still ABI 7: allred_bucket and allred_plan_execute_group / allred_plan_reduce_scatter_group /
+ * allred_plan_group_launches are additions — a list of buckets, the small ones sharing launches. */
 #define ALLRED_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------- */
@@ -272,6 +274,52 @@ int allred_plan_all_gather(allred_plan* plan, uint16_t* ranks, uint64_t rank_str
                            uint64_t in_stride, void* workspace, void* stream);
 /* number of kernel launches one execute enqueues (for per-launch accounting) */
 int allred_plan_launches(const allred_plan* plan);
+
+/* GROUPED calls: a list of buckets of different sizes — a training step's gradient buckets —
+ * through the fused BO allreduce or its reduce-scatter in place, the small ones sharing kernel
+ * launches (a fused pass below about 1024 tiles at 64 ranks is launch-bound: sixteen 32 kB
+ * buckets cost sixteen launch latencies one by one).  The plan supplies the SCHEDULE only — algo,
+ * side, total, the tree order table —; each bucket brings its own size, the plan's
+ * elems_per_rank is not used.  Accepted plans: ALLRED_BO with ALLRED_EXEC_FUSED, any BO grid, 2D
+ * or 1D algo; LO / MEM plans and steps-form plans: ALLRED_ERR_UNSUPPORTED.  No reference
+ * counterpart (the reference runs one vector per program).
+ *   execute_group         every bucket ends with exactly the bits allred_plan_execute of a fused
+ *                         BO plan of that bucket's size gives it (block b = tree b, every add
+ *                         rounded to bf16).
+ *   reduce_scatter_group  block b of rank b's row of every bucket receives those bits and nothing
+ *                         else is written (the other blocks, the stride skew, memory past a row),
+ *                         as allred_plan_reduce_scatter in place.  Out of place: not in the group.
+ * Checks, all made before the first launch (a refused call writes nothing), ALLRED_ERR_ARG:
+ * count < 0; buckets == NULL with count > 0; per bucket allred_plan_execute's rules (ranks NULL
+ * or not 16-byte aligned, elems_per_rank == 0 or % (8 * total) != 0, rank_stride <
+ * elems_per_rank or % 8 != 0); the 256-element tiles of all buckets together past 2^31 - 1
+ * (32-bit tile indices); the ranges [ranks, ranks + total * rank_stride) of two buckets
+ * overlapping.  count == 0: ALLRED_OK, nothing launched.  total == 1: a no-op.
+ * Routing, per bucket, on the host.  A bucket keeps its own route — its own launch(es), enqueued
+ * at its place in the list — when that route is the persistent 64-rank pass (64 ranks, whole
+ * tiles, >= 1024 tiles, fused_form 0: HBM-bound, not launch-bound) or when it is not whole tiles
+ * (total < 8 or elems_per_rank % (256 * total) != 0).  Every other bucket is whole tiles of 8 ..
+ * 64 ranks: these are gathered, at most ALLRED_GROUP_MAX at a time, into ONE launch of
+ * k_tree_group, enqueued when its last member is reached (the ALLRED_GROUP_MAX-th, or the end of
+ * the list).  All launches go to `stream`; the buckets are disjoint, so their order among each
+ * other does not matter.  The tune key pipe_grid caps the grouped grid like every persistent
+ * pass; fused_form 1 or 2 turns grouping off (every bucket its own launch).  The memory type of a
+ * bucket is not looked at (pinned host buckets work, without allred_plan_execute's narrow grid).
+ * The grouped launch's table travels in the kernel arguments: no allocation, no copy, so the
+ * calls can be captured into a graph.
+ *   group_launches        the kernel launches execute_group would enqueue for the list with the
+ *                         tune keys as they are now (reduce_scatter_group: the same, except that
+ *                         a bucket on the persistent 64-rank route is always one launch), or a
+ *                         negative status for arguments the call would refuse. */
+#define ALLRED_GROUP_MAX 64            /* buckets one grouped launch covers */
+typedef struct {
+    uint16_t* ranks;                   /* rank r of this bucket at ranks + r * rank_stride */
+    uint64_t  rank_stride;             /* elements */
+    uint64_t  elems_per_rank;          /* this bucket's n; the plan's own elems_per_rank is not used */
+} allred_bucket;
+int allred_plan_execute_group(allred_plan* plan, const allred_bucket* buckets, int count, void* stream);
+int allred_plan_reduce_scatter_group(allred_plan* plan, const allred_bucket* buckets, int count, void* stream);
+int allred_plan_group_launches(const allred_plan* plan, const allred_bucket* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -236,6 +236,33 @@ class Plan:
         check(lib.allred_plan_all_gather(self._h, ranks_ptr, stride, in_ptr or None, in_stride, workspace_ptr,
                                          _stream_ptr(stream)), "plan_all_gather")
 
+    @staticmethod
+    def _buckets(buckets):
+        """a sequence of (ranks_ptr, stride, elems_per_rank) as an allred_bucket array (None when empty)"""
+        items = [(int(p), int(s), int(n)) for p, s, n in buckets]
+        return ((_lib.Bucket * len(items))(*items) if items else None), len(items)
+
+    def execute_group(self, buckets, stream=None) -> None:
+        """allred_plan_execute_group (fused BO plans): the BO allreduce of every (ranks_ptr, stride,
+        elems_per_rank) of the list, the small whole-tile buckets sharing kernel launches; the
+        plan supplies the schedule only."""
+        arr, count = self._buckets(buckets)
+        check(lib.allred_plan_execute_group(self._h, arr, count, _stream_ptr(stream)), "plan_execute_group")
+
+    def reduce_scatter_group(self, buckets, stream=None) -> None:
+        """allred_plan_reduce_scatter_group: the in-place reduce-scatter of every bucket of the list."""
+        arr, count = self._buckets(buckets)
+        check(lib.allred_plan_reduce_scatter_group(self._h, arr, count, _stream_ptr(stream)),
+              "plan_reduce_scatter_group")
+
+    def group_launches(self, buckets) -> int:
+        """Kernel launches execute_group would enqueue for the list now (with the current tune keys)."""
+        arr, count = self._buckets(buckets)
+        st = lib.allred_plan_group_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_group_launches")
+        return st
+
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
         st = np.ascontiguousarray(stamps, dtype=np.uint64)

@@ -122,6 +122,13 @@ class RankCheck(C.Structure):
     _fields_ = [("bad", C.c_uint64), ("first_bad", C.c_uint64), ("max_error", C.c_float), ("reserved", C.c_int32)]
 
 
+GROUP_MAX = 64   # ALLRED_GROUP_MAX: buckets one grouped launch covers
+
+
+class Bucket(C.Structure):   # allred_bucket
+    _fields_ = [("ranks", C.c_void_p), ("rank_stride", C.c_uint64), ("elems_per_rank", C.c_uint64)]
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -165,6 +172,9 @@ SIGNATURES = [
     ("allred_plan_reduce_scatter", C.c_int, [_P, _u16p, C.c_uint64, _u16p, C.c_uint64, _P, _P]),
     ("allred_plan_all_gather", C.c_int, [_P, _u16p, C.c_uint64, _u16p, C.c_uint64, _P, _P]),
     ("allred_plan_launches", C.c_int, [_P]),
+    ("allred_plan_execute_group", C.c_int, [_P, C.POINTER(Bucket), C.c_int, _P]),
+    ("allred_plan_reduce_scatter_group", C.c_int, [_P, C.POINTER(Bucket), C.c_int, _P]),
+    ("allred_plan_group_launches", C.c_int, [_P, C.POINTER(Bucket), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

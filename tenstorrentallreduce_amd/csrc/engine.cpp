@@ -16,6 +16,7 @@
 // when every rank's tree is the same (lo_rank_uniform), MEM: k_mem*).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +31,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "tile_span.hpp"
 
 using namespace tsa;
 
@@ -835,6 +837,66 @@ int allred_plan_all_gather(allred_plan* p, uint16_t* ranks, uint64_t stride, con
         st = launch_ag_step(ranks, stride, N, p->d_partner + (size_t)k * N, p->d_ag_blocks + p->blk_off[k],
                             p->blk_per_rank[k], p->block_elems, stream);
     return st;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The checks of the grouped calls, all before any HIP call: the plan (a fused BO plan supplies
+// the schedule), the list, every bucket by allred_plan_execute's rules, the tiles of all buckets
+// together in 32 bits, and no two buckets' rank rows overlapping.
+int group_check(const allred_plan* p, const allred_bucket* buckets, int count) {
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count == 0) return ALLRED_OK;
+    if (!buckets) return ALLRED_ERR_ARG;
+    const uint64_t total = (uint64_t)p->total;
+    uint64_t tiles = 0;
+    std::vector<std::pair<uintptr_t, uintptr_t>> span((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_bucket& b = buckets[i];
+        const uint64_t n = b.elems_per_rank, stride = b.rank_stride;
+        if (!b.ranks || (uintptr_t)b.ranks % 16 || n == 0 || n % (8 * total) || stride < n || stride % 8)
+            return ALLRED_ERR_ARG;
+        const uint64_t t = (n + 255) / 256;
+        if (t > kTileSpanMaxTiles - tiles) return ALLRED_ERR_ARG;   // 32-bit tile indices (group_span.hpp)
+        tiles += t;
+        if (stride > (UINTPTR_MAX - (uintptr_t)b.ranks) / (2 * total)) return ALLRED_ERR_ARG;
+        span[(size_t)i] = {(uintptr_t)b.ranks, (uintptr_t)b.ranks + 2 * (uintptr_t)(total * stride)};
+    }
+    std::sort(span.begin(), span.end());
+    for (int i = 1; i < count; ++i)
+        if (span[(size_t)i].first < span[(size_t)i - 1].second) return ALLRED_ERR_ARG;
+    return ALLRED_OK;
+}
+
+int group_run(allred_plan* p, const allred_bucket* buckets, int count, bool write_all, void* stream) {
+    const int st = group_check(p, buckets, count);
+    if (st != ALLRED_OK || count == 0 || p->total == 1) return st;   // one rank: nothing to reduce
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_tree_group(buckets, count, p->total, p->desc.algo, p->desc.side_length, p->d_order, write_all,
+                             /*dry=*/false, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {
+    return group_run(p, buckets, count, true, stream);
+}
+
+int allred_plan_reduce_scatter_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {
+    return group_run(p, buckets, count, false, stream);
+}
+
+int allred_plan_group_launches(const allred_plan* p, const allred_bucket* buckets, int count) {
+    const int st = group_check(p, buckets, count);
+    if (st != ALLRED_OK || count == 0 || p->total == 1) return st;
+    return launch_tree_group(buckets, count, p->total, p->desc.algo, p->desc.side_length, p->d_order, true,
+                             /*dry=*/true, nullptr);
 }
 
 int allred_bf16_add(uint16_t* dst, const uint16_t* src, size_t n, void* stream) {

@@ -82,6 +82,12 @@ int launch_reduce_scatter(uint16_t* ranks, uint64_t stride, size_t n, int total,
                           uint64_t out_stride, void* stream);
 int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, const uint16_t* in, uint64_t in_stride,
                       void* stream);
+// a list of (checked) buckets through the fused BO pass (write_all) or its in-place reduce-scatter:
+// whole-tile buckets of 8 .. 64 ranks below the persistent 64-rank pass's size share launches of
+// k_tree_group, up to ALLRED_GROUP_MAX buckets each; the others take their own route.  dry: launch
+// nothing, return the number of kernel launches instead of a status
+int launch_tree_group(const allred_bucket* buckets, int count, int total, int algo, int side, const uint8_t* order,
+                      bool write_all, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,

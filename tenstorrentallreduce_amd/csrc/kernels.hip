@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "device.hpp"
+#include "group_span.hpp"
 #include "tile_span.hpp"
 
 namespace tsa {
@@ -268,6 +269,85 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
         if (block_vec == 0) return tiles(std::true_type{});
     }
     tiles(std::false_type{});
+}
+
+// ---------------------------------------------------------------------------
+// k_tree_group: k_tree_lds_pipe's pass over the concatenated tile ranges of up
+// to 64 BUCKETS in one launch (allred_plan_execute_group /
+// allred_plan_reduce_scatter_group: a list of small gradient buckets costs one
+// launch latency instead of one per bucket).  Same schedule — persistent grid,
+// two LDS tile buffers loaded by LDS-DMA, the order table staged once, the
+// same ops in the same order on the vmcnt counter, hence the same waits — and
+// the same tree (tree_wave_part / tree_join4).  What differs is where a tile
+// lives: its bucket's row 0, stride and block come from the host's table
+// (GroupSpan, group_span.hpp, passed by value: scalar loads from the kernel
+// arguments, no division), located with a cursor that only walks forward.  The
+// next tile is located before the wait for the current one, so the table reads
+// overlap the loads in flight.  WRITE_ALL: the result to all P rows of the
+// tile's bucket; else one row, to rank b's own row of it (tree_dst, out == nullptr).
+// ---------------------------------------------------------------------------
+template <int P, bool WRITE_ALL>
+__global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict__ order, GroupSpan span) {
+    constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
+    static_assert(OPS >= 1, "P >= 8");
+    __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
+    __shared__ __attribute__((aligned(16))) uint4 part[4 * TV];
+    __shared__ __attribute__((aligned(16))) uint8_t ord_lds[P * ALLRED_MAX_NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    const uint32_t wbase = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
+    struct Tile {
+        uint16_t* ranks;   // the bucket's row 0
+        uint64_t stride;
+        uint64_t v0;       // the tile's first 16-byte vector inside a rank row
+        uint32_t block;
+    };
+    uint32_t cursor = 0;   // wave-uniform: it depends on blockIdx and j only
+    auto locate = [&](int j) {
+        const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
+        return Tile{span.b[gt.bucket].ranks, span.b[gt.bucket].stride, (uint64_t)gt.local * TV, gt.block};
+    };
+    auto issue = [&](const Tile& t, int b) {
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            const int r = RPW * w + RPI * k + q;
+            const uint4* src = reinterpret_cast<const uint4*>(t.ranks + (uint64_t)r * t.stride) + t.v0 + c;
+            lds_dma16(src, wbase + (uint32_t)(b * P * TV * 16 + RPI * k * TV * 16));
+        }
+    };
+    const int mine = (int)group_span_mine(span, blockIdx.x);
+    // the order rows of all P blocks, once, then the first tile's loads
+    for (int i = threadIdx.x; i < P * ALLRED_MAX_NODES / 16; i += kBlock)
+        reinterpret_cast<uint4*>(ord_lds)[i] = reinterpret_cast<const uint4*>(order)[i];
+    __syncthreads();
+    if (mine <= 0) return;
+    Tile cur = locate(0), nxt = cur;
+    issue(cur, 0);
+    for (int j = 0; j < mine; ++j) {
+        if (j + 1 < mine) nxt = locate(j + 1);
+        if (WRITE_ALL) wait_tile<OPS, 1>(j < 1 ? j : 1);
+        else if (j > 0 && w == 0) wait_vm<1>();   // tile j-1's result store may stay in flight
+        else wait_vm<0>();
+        lds_barrier();
+        if (j + 1 < mine) issue(nxt, (j + 1) & 1);
+        const uint4* tile = buf[j & 1];
+        const uint4 pw = tree_wave_part<TV, LPL>(tile, ord_lds + cur.block * ALLRED_MAX_NODES + RPW * w + LPL * q, c);
+        if (q == 0) part[w * TV + c] = pw;
+        lds_barrier();
+        if (!WRITE_ALL) {
+            if (w == 0 && q == 0)
+                st_nt(tree_dst(cur.ranks, cur.stride, nullptr, 0, cur.block, cur.v0 + c, 0), tree_join4<TV>(part, c));
+        } else {
+            const uint4 res = tree_join4<TV>(part, c);
+#pragma unroll
+            for (int k = 0; k < OPS; ++k) {
+                const int r = RPW * w + RPI * k + q;
+                st_nt(reinterpret_cast<uint4*>(cur.ranks + (uint64_t)r * cur.stride) + cur.v0 + c, res);
+            }
+        }
+        cur = nxt;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1894,6 +1974,63 @@ int launch_reduce_scatter(uint16_t* ranks, uint64_t stride, size_t n, int total,
         (out && (out_stride % 8 || !aligned16(out))))
         return ALLRED_ERR_ARG;
     return tree_dispatch<false>(ranks, stride, n / 8, total, order, n / 8 / total, out, out_stride, (hipStream_t)stream);
+}
+
+// A list of buckets through the fused BO pass (write_all) or its reduce-scatter in place, routed
+// per bucket on the host.  A bucket keeps its own route — launch_tree_fused / launch_reduce_scatter,
+// at its place in the list — when that route is the persistent 64-rank pass of >= 1024 tiles
+// (HBM-bound: k_tree_lds_lag is the measured best) or when it is not whole tiles (total < 8,
+// n % (256 total) != 0: tree_dispatch's register form).  Every other bucket is whole tiles of
+// 8 .. 64 ranks: these are gathered, kGroupMax at a time, into ONE launch of k_tree_group, enqueued
+// when its last member is reached (the kGroupMax-th, or the end of the list).  fused_form 1 / 2
+// (the A/B forms without a persistent grid) turn grouping off.  dry: nothing is launched and the
+// number of launches is returned.  The arguments are checked by the caller (engine.cpp group_check).
+int launch_tree_group(const allred_bucket* buckets, int count, int total, int algo, int side, const uint8_t* order,
+                      bool write_all, bool dry, void* stream) {
+    const int64_t form = fused_form();
+    hipStream_t st = (hipStream_t)stream;
+    GroupIn in[kGroupMax];
+    int pending = 0, launches = 0;
+    uint64_t pending_tiles = 0;
+    auto flush = [&]() -> int {
+        if (!pending) return ALLRED_OK;
+        ++launches;
+        const int members = pending;
+        const uint64_t tiles = pending_tiles;
+        pending = 0;
+        pending_tiles = 0;
+        if (dry) return ALLRED_OK;
+        const unsigned grid = persistent_grid(tiles, 512);
+        GroupSpan span;
+        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+        const bool found = for_ranks<8, 64>(total, [&](auto p) {
+            if (write_all) hipLaunchKernelGGL((k_tree_group<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span);
+            else hipLaunchKernelGGL((k_tree_group<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span);
+        });
+        return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
+    };
+    for (int i = 0; i < count; ++i) {
+        const allred_bucket& b = buckets[i];
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
+        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
+        int s = ALLRED_OK;
+        if (whole_tiles && !lag64 && form != 1 && form != 2) {
+            in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
+            pending_tiles += tiles;
+            if (pending == kGroupMax) s = flush();
+        } else {
+            launches += write_all ? (int)fused_launches(ALLRED_BO, false, algo, side, b.elems_per_rank, total) : 1;
+            if (!dry)
+                s = write_all ? launch_tree_fused(b.ranks, b.rank_stride, b.elems_per_rank, total, order, stream)
+                              : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, nullptr, 0,
+                                                      stream);
+        }
+        if (s != ALLRED_OK) return s;
+    }
+    const int s = flush();
+    if (s != ALLRED_OK) return s;
+    return dry ? launches : ALLRED_OK;
 }
 
 int launch_tree_bcast_x(uint16_t* cur, uint16_t* prev, uint64_t stride, size_t n, int total, const uint8_t* order,
