@@ -34,7 +34,10 @@ extern "C" {
  * allred_dist_all_gather (+ their _host twins) are additions too — the two halves of the BO
  * allreduce as calls of their own, on the existing plans, descs and communicators.
  * Still ABI 7: allred_bucket and allred_plan_execute_group / allred_plan_reduce_scatter_group /
- * allred_plan_group_launches are additions — a list of buckets, the small ones sharing launches. */
+ * allred_plan_group_launches are additions — a list of buckets, the small ones sharing launches.
+ * Still ABI 7: allred_shard_bucket and allred_plan_reduce_scatter_shards / allred_plan_all_gather_shards /
+ * allred_plan_shards_launches are additions — the grouped reduce-scatter into, and the grouped
+ * all-gather from, per-bucket shard buffers. */
 #define ALLRED_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------- */
@@ -288,7 +291,8 @@ int allred_plan_launches(const allred_plan* plan);
  *                         rounded to bf16).
  *   reduce_scatter_group  block b of rank b's row of every bucket receives those bits and nothing
  *                         else is written (the other blocks, the stride skew, memory past a row),
- *                         as allred_plan_reduce_scatter in place.  Out of place: not in the group.
+ *                         as allred_plan_reduce_scatter in place.  Out of place: not in this call
+ *                         (allred_plan_reduce_scatter_shards below).
  * Checks, all made before the first launch (a refused call writes nothing), ALLRED_ERR_ARG:
  * count < 0; buckets == NULL with count > 0; per bucket allred_plan_execute's rules (ranks NULL
  * or not 16-byte aligned, elems_per_rank == 0 or % (8 * total) != 0, rank_stride <
@@ -320,6 +324,71 @@ typedef struct {
 int allred_plan_execute_group(allred_plan* plan, const allred_bucket* buckets, int count, void* stream);
 int allred_plan_reduce_scatter_group(allred_plan* plan, const allred_bucket* buckets, int count, void* stream);
 int allred_plan_group_launches(const allred_plan* plan, const allred_bucket* buckets, int count);
+
+/* GROUPED calls WITH SHARD BUFFERS: the two halves of a sharded (ZeRO / FSDP) training step over
+ * the step's whole list of buckets — reduce-scatter every gradient bucket into each rank's shard,
+ * (the optimizer runs on the shards,) all-gather every parameter bucket from the shards — two
+ * launches per step where the per-bucket calls cost one each.  The plans, the checks and the
+ * routing are the grouped calls' above: ALLRED_BO with ALLRED_EXEC_FUSED, any BO grid, 2D or 1D
+ * algo (LO / MEM plans and steps-form plans: ALLRED_ERR_UNSUPPORTED); the plan supplies the
+ * SCHEDULE only.  Per bucket blk = elems_per_rank / total, and shard == NULL means in place.
+ * No reference counterpart (the reference runs one vector per program).
+ *   reduce_scatter_shards  block b of every bucket receives the bits allred_plan_execute of a
+ *                          fused plan of that size gives block b (tree b, every add rounded to
+ *                          bf16).  In place it goes to rank b's own row and nothing else is
+ *                          written: exactly allred_plan_reduce_scatter_group.  With a shard it
+ *                          goes to shard + b * shard_stride and `ranks` is only read; every byte
+ *                          outside the P blocks of blk elements keeps its bits, the gaps of a
+ *                          shard_stride > blk included.
+ *   all_gather_shards      block b of rank b — or of the shard — is copied, all 16 bits, NaN
+ *                          payloads included, to block b of every rank.  From a shard rank b is
+ *                          written too and the shard is only read; in place the owner's row is
+ *                          not rewritten.  Only the n elements of each row are written.
+ * Buckets with and without a shard may be mixed in one list.  reduce_scatter_shards then
+ * all_gather_shards on the same list = allred_plan_execute_group, bit for bit, in place and
+ * through shards.
+ * Checks, all made before the first launch (a refused call writes nothing), ALLRED_ERR_ARG: those
+ * of the grouped calls above for count, buckets and every bucket's ranks / rank_stride /
+ * elems_per_rank, the 2^31 - 1 tile cap over the whole list included; with a shard, shard_stride
+ * < blk, shard_stride % 8 != 0, a shard not 16-byte aligned, address arithmetic that would
+ * overflow; an `op` other than the two constants.  count == 0: ALLRED_OK, nothing launched.
+ * total == 1: a bucket in place is a no-op, one with a shard is copied by its per-bucket route.
+ * DISJOINTNESS, one rule for both calls (csrc/shard_ranges.hpp): the byte sets of one list must
+ * be pairwise disjoint, else ALLRED_ERR_ARG.  Every bucket's set is ONE interval, [ranks, ranks +
+ * total * rank_stride) — the grouped calls' rule, the stride skew counts.  Every shard's set is
+ * its `total` SEPARATE block intervals [shard + b * shard_stride, + blk); the range enclosing
+ * them is not used.  Block-exact on purpose: a sharded optimizer's buffer is rank-major — one row
+ * of F elements per rank, bucket i's shard at flat + off_i with shard_stride = F —, so the
+ * enclosing ranges of different buckets interleave and are accepted, as are another bucket's
+ * blocks in the gaps of a wide shard_stride.  Two buckets naming one shard are refused, in the
+ * all-gather, which only reads it, as well.
+ * Routing, per bucket, on the host, is the grouped calls' rule unchanged: a bucket keeps its own
+ * launch, at its place in the list, when it is not whole tiles (total < 8 or elems_per_rank %
+ * (256 * total) != 0) or when it has 64 ranks and >= 1024 tiles with fused_form 0; it then goes
+ * through the per-bucket route of allred_plan_reduce_scatter(.., out, out_stride) /
+ * allred_plan_all_gather(.., in, in_stride).  fused_form 1 / 2 turn grouping off.  Every other
+ * bucket shares one launch per ALLRED_GROUP_MAX members: k_tree_group (no member with a shard),
+ * k_tree_group with the shard table, or k_ag_group — the shard pointers travel in a second by-value table, so
+ * these calls, too, can be captured into a graph.  No new tune keys: pipe_grid caps the grids
+ * like every persistent pass.  The 1024-tile threshold was measured for the tree passes; nobody
+ * has measured it for the all-gather, which INHERITS it so that the two halves of a step route
+ * alike (one point next to it: DESIGN.md §12).
+ *   shards_launches        the kernel launches the call for `op` would enqueue for the list with
+ *                          the tune keys as they are now, or a negative status for arguments the
+ *                          call would refuse. */
+typedef struct {
+    uint16_t* ranks;                   /* as allred_bucket */
+    uint64_t  rank_stride;
+    uint64_t  elems_per_rank;
+    uint16_t* shard;                   /* NULL: in place.  Else block b of this bucket lives at
+                                          shard + b * shard_stride, blk = elems_per_rank / total elements */
+    uint64_t  shard_stride;            /* elements; ignored when shard == NULL */
+} allred_shard_bucket;
+#define ALLRED_OP_REDUCE_SCATTER 0
+#define ALLRED_OP_ALL_GATHER 1
+int allred_plan_reduce_scatter_shards(allred_plan* plan, const allred_shard_bucket* buckets, int count, void* stream);
+int allred_plan_all_gather_shards(allred_plan* plan, const allred_shard_bucket* buckets, int count, void* stream);
+int allred_plan_shards_launches(const allred_plan* plan, const allred_shard_bucket* buckets, int count, int op);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

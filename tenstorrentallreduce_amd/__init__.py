@@ -18,8 +18,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ACC_BF16, ACC_FP32, BO, EXEC_FUSED, EXEC_STEPS, LO, MEM, MULTI_FLAT, MULTI_HIER,  # noqa: F401
-                   MULTI_LOCAL, RECDUB, RECDUB_1D, SWING, SWING_1D, TRANSPORT_HOST, TRANSPORT_PEER, TRANSPORT_RCCL,
-                   AllredError, Args, DistDesc, MultiOpts, MultiPlan, PlanDesc, Report, Schedule, Seg, check, lib)
+                   MULTI_LOCAL, OP_ALL_GATHER, OP_REDUCE_SCATTER, RECDUB, RECDUB_1D, SWING, SWING_1D, TRANSPORT_HOST,
+                   TRANSPORT_PEER, TRANSPORT_RCCL, AllredError, Args, DistDesc, MultiOpts, MultiPlan, PlanDesc, Report, Schedule, Seg, check, lib)
 
 __all__ = [
     "BO", "LO", "MEM", "SWING", "RECDUB", "SWING_1D", "RECDUB_1D", "get_comm_partner_swing_1D",
@@ -32,7 +32,7 @@ __all__ = [
     "ACC_FP32",
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
-    "dist_reduce_scatter_host", "dist_all_gather_host",
+    "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
 ]
 
 
@@ -261,6 +261,40 @@ class Plan:
         st = lib.allred_plan_group_launches(self._h, arr, count)
         if st < 0:
             raise AllredError(st, "plan_group_launches")
+        return st
+
+    @staticmethod
+    def _shard_buckets(buckets):
+        """a sequence of (ranks_ptr, stride, elems_per_rank) — in place — or (ranks_ptr, stride,
+        elems_per_rank, shard_ptr, shard_stride) as an allred_shard_bucket array (None when empty)"""
+        items = []
+        for b in buckets:
+            p, s, n = b[:3]
+            shard, shard_stride = b[3:] if len(b) > 3 else (None, 0)
+            items.append((int(p), int(s), int(n), int(shard) if shard else None, int(shard_stride)))
+        return ((_lib.ShardBucket * len(items))(*items) if items else None), len(items)
+
+    def reduce_scatter_shards(self, buckets, stream=None) -> None:
+        """allred_plan_reduce_scatter_shards (fused BO plans): the reduce-scatter of every bucket of
+        the list, block b to rank b's row (3-tuples) or to shard_ptr + b * shard_stride elements
+        (5-tuples, the rank rows only read); the small whole-tile buckets share kernel launches."""
+        arr, count = self._shard_buckets(buckets)
+        check(lib.allred_plan_reduce_scatter_shards(self._h, arr, count, _stream_ptr(stream)),
+              "plan_reduce_scatter_shards")
+
+    def all_gather_shards(self, buckets, stream=None) -> None:
+        """allred_plan_all_gather_shards: block b of rank b — or of the bucket's shard — copied bit
+        for bit to block b of every rank, for every bucket of the list."""
+        arr, count = self._shard_buckets(buckets)
+        check(lib.allred_plan_all_gather_shards(self._h, arr, count, _stream_ptr(stream)), "plan_all_gather_shards")
+
+    def shards_launches(self, buckets, op: int) -> int:
+        """Kernel launches reduce_scatter_shards (op = OP_REDUCE_SCATTER) or all_gather_shards
+        (OP_ALL_GATHER) would enqueue for the list now (with the current tune keys)."""
+        arr, count = self._shard_buckets(buckets)
+        st = lib.allred_plan_shards_launches(self._h, arr, count, op)
+        if st < 0:
+            raise AllredError(st, "plan_shards_launches")
         return st
 
     def rank_zones(self, stamps: np.ndarray):

@@ -129,6 +129,14 @@ class Bucket(C.Structure):   # allred_bucket
     _fields_ = [("ranks", C.c_void_p), ("rank_stride", C.c_uint64), ("elems_per_rank", C.c_uint64)]
 
 
+class ShardBucket(C.Structure):   # allred_shard_bucket: shard None / 0 = in place
+    _fields_ = [("ranks", C.c_void_p), ("rank_stride", C.c_uint64), ("elems_per_rank", C.c_uint64),
+                ("shard", C.c_void_p), ("shard_stride", C.c_uint64)]
+
+
+OP_REDUCE_SCATTER, OP_ALL_GATHER = 0, 1   # ALLRED_OP_*: allred_plan_shards_launches' op
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -175,6 +183,9 @@ SIGNATURES = [
     ("allred_plan_execute_group", C.c_int, [_P, C.POINTER(Bucket), C.c_int, _P]),
     ("allred_plan_reduce_scatter_group", C.c_int, [_P, C.POINTER(Bucket), C.c_int, _P]),
     ("allred_plan_group_launches", C.c_int, [_P, C.POINTER(Bucket), C.c_int]),
+    ("allred_plan_reduce_scatter_shards", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, _P]),
+    ("allred_plan_all_gather_shards", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, _P]),
+    ("allred_plan_shards_launches", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -31,6 +31,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "shard_ranges.hpp"
 #include "tile_span.hpp"
 
 using namespace tsa;
@@ -880,9 +881,57 @@ int group_run(allred_plan* p, const allred_bucket* buckets, int count, bool writ
                              /*dry=*/false, stream);
 }
 
+// The checks of the grouped shard calls, all before any HIP call: group_check's on the plan, the
+// list and every bucket's rank rows; the shard rules (stride, alignment); then the one
+// disjointness rule over rank rows and shard BLOCKS (shard_ranges.hpp), which also refuses
+// address arithmetic that would overflow.
+int shards_check(const allred_plan* p, const allred_shard_bucket* buckets, int count, int op) {
+    if (op != ALLRED_OP_REDUCE_SCATTER && op != ALLRED_OP_ALL_GATHER) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count == 0) return ALLRED_OK;
+    if (!buckets) return ALLRED_ERR_ARG;
+    std::vector<allred_bucket> plain((size_t)count);
+    for (int i = 0; i < count; ++i)
+        plain[(size_t)i] = allred_bucket{buckets[i].ranks, buckets[i].rank_stride, buckets[i].elems_per_rank};
+    const int st = group_check(p, plain.data(), count);
+    if (st != ALLRED_OK) return st;
+    const uint64_t total = (uint64_t)p->total;
+    std::vector<ShardRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_shard_bucket& b = buckets[i];
+        if (b.shard && (b.shard_stride < b.elems_per_rank / total || b.shard_stride % 8 || (uintptr_t)b.shard % 16))
+            return ALLRED_ERR_ARG;
+        ranges[(size_t)i] = ShardRange{b.ranks, b.rank_stride, b.elems_per_rank, b.shard, b.shard ? b.shard_stride : 0};
+    }
+    return shard_lists_disjoint(ranges.data(), count, total) ? ALLRED_OK : ALLRED_ERR_ARG;
+}
+
+int shards_run(allred_plan* p, const allred_shard_bucket* buckets, int count, int op, void* stream) {
+    const int st = shards_check(p, buckets, count, op);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_shard_group(buckets, count, p->total, p->d_order, op, /*dry=*/false, stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int allred_plan_reduce_scatter_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {
+    return shards_run(p, buckets, count, ALLRED_OP_REDUCE_SCATTER, stream);
+}
+
+int allred_plan_all_gather_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {
+    return shards_run(p, buckets, count, ALLRED_OP_ALL_GATHER, stream);
+}
+
+int allred_plan_shards_launches(const allred_plan* p, const allred_shard_bucket* buckets, int count, int op) {
+    const int st = shards_check(p, buckets, count, op);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_shard_group(buckets, count, p->total, p->d_order, op, /*dry=*/true, nullptr);
+}
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {
     return group_run(p, buckets, count, true, stream);

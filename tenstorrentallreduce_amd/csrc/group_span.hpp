@@ -44,6 +44,20 @@ struct GroupSpan {
 };
 static_assert(sizeof(GroupBucket) == 32 && sizeof(GroupSpan) == 16 + 32 * kGroupMax, "the kernel-argument layout");
 
+// The shard buffers of a grouped launch (allred_plan_reduce_scatter_shards /
+// allred_plan_all_gather_shards): a second by-value table next to GroupSpan, entry i for bucket
+// i of the launch — block b of the bucket lives at shard + b * stride elements, or, shard ==
+// nullptr, in rank b's own row (in place).  64 x 16 bytes: with the order pointer and GroupSpan
+// 8 + 2064 + 1024 = 3096 bytes of kernel arguments, inside the 4 KiB limit.
+struct GroupShard {        // 16 bytes
+    uint16_t* shard;
+    uint64_t stride;       // elements
+};
+struct GroupShards {
+    GroupShard s[kGroupMax];    // entries past the last bucket: zero
+};
+static_assert(sizeof(GroupShard) == 16 && sizeof(GroupShards) == 16 * kGroupMax, "the kernel-argument layout");
+
 // what the host knows of a bucket: `tiles` 256-element tiles per rank row in blocks of tpb tiles
 struct GroupIn {
     uint16_t* ranks;

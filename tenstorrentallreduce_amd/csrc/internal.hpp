@@ -88,6 +88,12 @@ int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, con
 // nothing, return the number of kernel launches instead of a status
 int launch_tree_group(const allred_bucket* buckets, int count, int total, int algo, int side, const uint8_t* order,
                       bool write_all, bool dry, void* stream);
+// a list of (checked) buckets, each in place or with a shard buffer, through the reduce-scatter or
+// the all-gather (op: ALLRED_OP_*), routed per bucket by launch_tree_group's rule: the grouped
+// buckets share launches of k_tree_group (with its shard table) / k_ag_group, the others go through
+// launch_reduce_scatter / launch_all_gather.  dry: launch nothing, return the number of launches
+int launch_shard_group(const allred_shard_bucket* buckets, int count, int total, const uint8_t* order, int op, bool dry,
+                       void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,

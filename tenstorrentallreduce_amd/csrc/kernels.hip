@@ -285,9 +285,22 @@ __global__ __launch_bounds__(kBlock) void k_tree_lds_pipe(uint16_t* __restrict__
 // next tile is located before the wait for the current one, so the table reads
 // overlap the loads in flight.  WRITE_ALL: the result to all P rows of the
 // tile's bucket; else one row, to rank b's own row of it (tree_dst, out == nullptr).
+// The kernel takes an optional second by-value table, GroupShards (the parameter pack SH:
+// empty, or that one type).  Without it — k_tree_group<P, WRITE_ALL>, the in-place forms
+// above — the kernel is what it always was, argument list, code and resources.  With it —
+// k_tree_group<P, false, GroupShards>, allred_plan_reduce_scatter_shards; one row only —
+// bucket i's block b goes to shards.s[i].shard + b * stride — tree_dst's `out` /
+// `out_stride` with block_vec = the bucket's tiles per block x 32 —, or, where the entry's
+// shard is null, to rank b's row as before, so one launch mixes buckets with and without a
+// shard.  With a shard the bucket's rows are only read.
 // ---------------------------------------------------------------------------
-template <int P, bool WRITE_ALL>
-__global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict__ order, GroupSpan span) {
+template <class T>
+__device__ __forceinline__ const T& group_table(const T& t) { return t; }
+
+template <int P, bool WRITE_ALL, class... SH>
+__global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict__ order, GroupSpan span, SH... shards) {
+    constexpr bool SHARDS = sizeof...(SH) == 1;
+    static_assert(sizeof...(SH) <= 1 && !(SHARDS && WRITE_ALL), "at most one table; a shard receives the one-row form only");
     constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
     static_assert(OPS >= 1, "P >= 8");
     __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
@@ -297,7 +310,12 @@ __global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict
     const int c = lane % TV, q = lane / TV;
     const uint32_t wbase = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
-    struct Tile {
+    struct NoOut {};
+    struct Out {           // tree_dst's arguments (SHARDS only): the bucket's shard (nullptr: in place), its
+        uint16_t* out;     // stride and the bucket's block length in 16-byte vectors
+        uint64_t out_stride, block_vec;
+    };
+    struct Tile : std::conditional_t<SHARDS, Out, NoOut> {
         uint16_t* ranks;   // the bucket's row 0
         uint64_t stride;
         uint64_t v0;       // the tile's first 16-byte vector inside a rank row
@@ -306,7 +324,18 @@ __global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict
     uint32_t cursor = 0;   // wave-uniform: it depends on blockIdx and j only
     auto locate = [&](int j) {
         const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
-        return Tile{span.b[gt.bucket].ranks, span.b[gt.bucket].stride, (uint64_t)gt.local * TV, gt.block};
+        Tile t;
+        t.ranks = span.b[gt.bucket].ranks;
+        t.stride = span.b[gt.bucket].stride;
+        t.v0 = (uint64_t)gt.local * TV;
+        t.block = gt.block;
+        if constexpr (SHARDS) {
+            const GroupShards& tab = group_table(shards...);
+            t.out = tab.s[gt.bucket].shard;
+            t.out_stride = tab.s[gt.bucket].stride;
+            t.block_vec = (uint64_t)span.b[gt.bucket].tpb * TV;
+        }
+        return t;
     };
     auto issue = [&](const Tile& t, int b) {
 #pragma unroll
@@ -336,8 +365,12 @@ __global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict
         if (q == 0) part[w * TV + c] = pw;
         lds_barrier();
         if (!WRITE_ALL) {
-            if (w == 0 && q == 0)
-                st_nt(tree_dst(cur.ranks, cur.stride, nullptr, 0, cur.block, cur.v0 + c, 0), tree_join4<TV>(part, c));
+            if (w == 0 && q == 0) {
+                uint4* dst;
+                if constexpr (SHARDS) dst = tree_dst(cur.ranks, cur.stride, cur.out, cur.out_stride, cur.block, cur.v0 + c, cur.block_vec);
+                else dst = tree_dst(cur.ranks, cur.stride, nullptr, 0, cur.block, cur.v0 + c, 0);
+                st_nt(dst, tree_join4<TV>(part, c));
+            }
         } else {
             const uint4 res = tree_join4<TV>(part, c);
 #pragma unroll
@@ -349,6 +382,96 @@ __global__ __launch_bounds__(kBlock) void k_tree_group(const uint8_t* __restrict
         cur = nxt;
     }
 }
+
+// ---------------------------------------------------------------------------
+// k_ag_group: the all-gather (k_ag's data movement) over the concatenated tile
+// ranges of up to 64 buckets in one launch (allred_plan_all_gather_shards),
+// walked exactly as k_tree_group walks them: persistent grid, workgroup g takes
+// tiles g + j * G, a forward-only wave-uniform cursor over GroupSpan, no
+// division.  Grouped buckets are whole tiles, so a tile lies in ONE block b and
+// its source row — rank b's row of the bucket, or shard + b * stride at the
+// tile's offset inside the block — is wave-uniform (k_ag, whose 64-vector runs
+// may cross blocks, computes it per lane).  Per tile every lane loads vector
+// c = lane % 32 of the 512-byte source tile and stores it to its rows
+// r = RPW w + RPI k + q: the WRITE_ALL store loop of k_tree_group, each wave
+// instruction two rows x 512 bytes.  In place (no shard) row r == b, the source,
+// is not rewritten; from a shard every row is written and the shard only read.
+// Tile j + 1 is located and its load issued before tile j's stores go out, and
+// the wait before them is an exact vmcnt that leaves it in flight, so a wave
+// never waits for a load with an empty store queue (k_ag's rule).  No LDS,
+// no barrier: the waves of a workgroup share nothing but the tile.  A vector of
+// a row is written by one wave instruction of the launch (in place, where the
+// owner's half redirects its store below, by two lanes of it with the same bits)
+// and the source vector by none, so nothing needs ordering.
+// ---------------------------------------------------------------------------
+template <int P>
+__global__ __launch_bounds__(kBlock) void k_ag_group(GroupSpan span, GroupShards shards) {
+    constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI;
+    static_assert(OPS >= 1, "P >= 8");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    struct Tile {
+        uint16_t* ranks;   // the bucket's row 0
+        uint64_t stride;
+        uint64_t v0;       // the tile's first 16-byte vector inside a rank row
+        uint32_t block;
+        bool in_place;
+        const uint4* src;  // the source tile's first vector
+    };
+    uint32_t cursor = 0;   // wave-uniform: it depends on blockIdx and j only
+    auto locate = [&](int j) {
+        const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
+        const GroupBucket& e = span.b[gt.bucket];
+        const GroupShard& sh = shards.s[gt.bucket];
+        Tile t{e.ranks, e.stride, (uint64_t)gt.local * TV, gt.block, sh.shard == nullptr, nullptr};
+        t.src = t.in_place ? reinterpret_cast<const uint4*>(e.ranks + (uint64_t)gt.block * e.stride) + t.v0
+                           : reinterpret_cast<const uint4*>(sh.shard + (uint64_t)gt.block * sh.stride) + (uint64_t)gt.rem * TV;
+        return t;
+    };
+    const int mine = (int)group_span_mine(span, blockIdx.x);
+    if (mine <= 0) return;
+    const int last = mine - 1;
+    // Every store of the loop is unconditional, so that the compiler, which counts the loads and
+    // stores itself, can put an exact vmcnt in front of a tile's stores (under an exec mask or a
+    // branch it has to assume the fewest operations behind a load on any path, and waits for
+    // everything: vmcnt(0) before every store, the next tile's load drained with the store queue
+    // empty).  In place, the lanes that hold the owner's row r == b do not skip their store: they
+    // store their neighbour half's row r ^ 1 — the row lane ^ 32 stores in the same instruction,
+    // same column, same bits — so row b is not written and nothing else is written twice with
+    // different data.
+    auto store = [&](const Tile& t, const uint4& x) {
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            const uint32_t r = (uint32_t)(RPW * w + RPI * k + q);
+            const uint32_t row = t.in_place && r == t.block ? r ^ 1u : r;
+            st_nt(reinterpret_cast<uint4*>(t.ranks + (uint64_t)row * t.stride) + t.v0 + c, x);
+        }
+    };
+    // Issue order per wave: L0 L1 S0 L2 S1 L3 S2 ...  Behind tile j's load come tile j - 1's OPS
+    // stores and tile j + 1's load, which stay in flight across the wait for tile j.  The load
+    // of the "next" tile is unconditional as well: a workgroup's last tile is loaded once more
+    // (an L2 hit).  Two tiles per trip, each with registers of its own: a tile's vector is never
+    // moved from a "next" to a "current" register, which would wait for the load it hides.
+    // Tile 0 is peeled, so that both waits of the loop see the same OPS + 1 operations behind
+    // their load on every path.
+    auto at = [&](int j) { return locate(j < last ? j : last); };
+    Tile a = locate(0);
+    uint4 xa = a.src[c];
+    Tile b = at(1);
+    uint4 xb = b.src[c];
+    store(a, xa);
+    for (int j = 1; j < mine; j += 2) {
+        a = at(j + 1);
+        xa = a.src[c];
+        store(b, xb);   // tile j
+        if (j + 1 >= mine) break;
+        b = at(j + 2);
+        xb = b.src[c];
+        store(a, xa);   // tile j + 1
+    }
+}
+// k_ag_group's resident cap (tune pipe_grid caps it lower): 8 four-wave workgroups per CU, as k_ag
+constexpr uint64_t kAgGroupGrid = kMaxGrid;
 
 // ---------------------------------------------------------------------------
 // k_tree_lds_lag: the fused BO pass (the bench kernel at config 2; same tree,
@@ -2025,6 +2148,81 @@ int launch_tree_group(const allred_bucket* buckets, int count, int total, int al
                 s = write_all ? launch_tree_fused(b.ranks, b.rank_stride, b.elems_per_rank, total, order, stream)
                               : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, nullptr, 0,
                                                       stream);
+        }
+        if (s != ALLRED_OK) return s;
+    }
+    const int s = flush();
+    if (s != ALLRED_OK) return s;
+    return dry ? launches : ALLRED_OK;
+}
+
+// A list of buckets, each in place or with a shard buffer, through the reduce-scatter
+// (ALLRED_OP_REDUCE_SCATTER) or the all-gather (ALLRED_OP_ALL_GATHER), routed per bucket by
+// launch_tree_group's rule unchanged: a bucket that is not whole tiles, or that has 64 ranks and
+// >= 1024 tiles with fused_form 0, keeps its own launch at its place in the list — the per-bucket
+// routes launch_reduce_scatter(.., out, out_stride) / launch_all_gather(.., in, in_stride) —;
+// fused_form 1 / 2 turn grouping off; every other bucket shares one launch per kGroupMax members:
+// k_tree_group<P, false> when no member has a shard (the launch allred_plan_reduce_scatter_group
+// makes), k_tree_group<P, false, GroupShards> when one has, k_ag_group<P> for the all-gather.  The 1024-tile
+// threshold was measured for the tree passes only; the all-gather inherits it so that the two
+// halves of a step route alike.  total == 1: an in-place bucket is a no-op (no launch), one with
+// a shard is copied by its per-bucket route.  dry: nothing is launched and the number of launches
+// is returned.  The arguments are checked by the caller (engine.cpp shards_check).
+int launch_shard_group(const allred_shard_bucket* buckets, int count, int total, const uint8_t* order, int op, bool dry,
+                       void* stream) {
+    const int64_t form = fused_form();
+    const bool gather = op == ALLRED_OP_ALL_GATHER;
+    hipStream_t st = (hipStream_t)stream;
+    GroupIn in[kGroupMax];
+    GroupShards shards{};
+    int pending = 0, launches = 0;
+    uint64_t pending_tiles = 0;
+    bool pending_shard = false;
+    auto flush = [&]() -> int {
+        if (!pending) return ALLRED_OK;
+        ++launches;
+        const int members = pending;
+        const uint64_t tiles = pending_tiles;
+        const bool with_shards = pending_shard;
+        pending = 0;
+        pending_tiles = 0;
+        pending_shard = false;
+        if (dry) return ALLRED_OK;
+        // the tree pass on 2 workgroups per CU like every tree pass; the copy, which holds no LDS, on
+        // up to kAgGroupGrid workgroups (measured against 512 and 2048: DESIGN.md §12)
+        const unsigned grid = persistent_grid(tiles, gather ? kAgGroupGrid : 512);
+        GroupSpan span;
+        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+        const bool found = for_ranks<8, 64>(total, [&](auto p) {
+            if (gather) hipLaunchKernelGGL((k_ag_group<p()>), dim3(grid), dim3(kBlock), 0, st, span, shards);
+            else if (with_shards)
+                hipLaunchKernelGGL((k_tree_group<p(), false, GroupShards>), dim3(grid), dim3(kBlock), 0, st, order, span,
+                                   shards);
+            else hipLaunchKernelGGL((k_tree_group<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span);
+        });
+        shards = GroupShards{};
+        return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
+    };
+    for (int i = 0; i < count; ++i) {
+        const allred_shard_bucket& b = buckets[i];
+        if (total == 1 && !b.shard) continue;   // one rank owns its one block already
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
+        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
+        int s = ALLRED_OK;
+        if (whole_tiles && !lag64 && form != 1 && form != 2) {
+            shards.s[pending] = GroupShard{b.shard, b.shard ? b.shard_stride : 0};
+            in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
+            pending_tiles += tiles;
+            pending_shard = pending_shard || b.shard;
+            if (pending == kGroupMax) s = flush();
+        } else {
+            ++launches;
+            if (!dry)
+                s = gather ? launch_all_gather(b.ranks, b.rank_stride, b.elems_per_rank, total, b.shard, b.shard_stride,
+                                               stream)
+                           : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, b.shard,
+                                                   b.shard_stride, stream);
         }
         if (s != ALLRED_OK) return s;
     }
