@@ -37,7 +37,9 @@ extern "C" {
  * allred_plan_group_launches are additions — a list of buckets, the small ones sharing launches.
  * Still ABI 7: allred_shard_bucket and allred_plan_reduce_scatter_shards / allred_plan_all_gather_shards /
  * allred_plan_shards_launches are additions — the grouped reduce-scatter into, and the grouped
- * all-gather from, per-bucket shard buffers. */
+ * all-gather from, per-bucket shard buffers.
+ * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
+ * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------- */
@@ -490,6 +492,25 @@ typedef struct {
     int32_t reserved;
 } allred_launch_info;
 int allred_last_launch(allred_launch_info* out);
+
+/* The launch trace of the calling thread: EVERY kernel the one-GPU engine (and the peer
+ * kernels allred_last_launch reports) launches between begin and end, in launch order.
+ * Names carry the template arguments ("k_tree_lds<16, true>", "k_mem_lds_lag<false>",
+ * "k_lo_dag_reg<LoDag0>"); a call that enqueues nothing records nothing.
+ * allred_launch_trace_begin arms the trace and clears it.  allred_launch_trace_end disarms
+ * it, copies the first min(cap, 64, *count) records to out and sets *count to the number of
+ * launches seen: the trace is a fixed ring of 64 records without allocation, launches beyond
+ * 64 are counted and not stored.  Disarmed, a launch pays one thread-local load and a branch.
+ * Launches made by other threads (the worker threads of allred_run_multi) are not seen.
+ * ALLRED_ERR_ARG: count NULL, cap < 0, out NULL with cap > 0, or end without begin.
+ * allred_last_launch neither feeds on nor is changed by the trace.  No reference counterpart. */
+typedef struct {
+    char kernel[64];
+    uint32_t grid;     /* workgroups (x; multiplied out when the grid is 2D) */
+    uint32_t block;
+} allred_launch_rec;
+int allred_launch_trace_begin(void);
+int allred_launch_trace_end(allred_launch_rec* out, int cap, int* count);
 
 /* ======================================================================
  * Reference program surface: AllredConfig (allred_helper.hpp:47-97) +

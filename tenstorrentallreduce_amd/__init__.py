@@ -28,7 +28,7 @@ __all__ = [
     "get_swing_block_comm_indexes", "get_recdub_block_comm_indexes", "normalize_tiles",
     "random_bf16_vector", "constant_bf16_vector", "validate_result_vector", "Plan", "preferred_rank_stride", "bf16_add",
     "bf16_add_masked", "tree_reduce", "broadcast", "parse_args", "run", "run_cli", "Comm", "dist_desc", "dist_allreduce",
-    "dist_allreduce_host", "dist_allreduce_pipelined", "tree_broadcast_pipelined", "dist_workspace_bytes", "dist_program_stats", "Peer", "tune", "tuned", "last_launch",
+    "dist_allreduce_host", "dist_allreduce_pipelined", "tree_broadcast_pipelined", "dist_workspace_bytes", "dist_program_stats", "Peer", "tune", "tuned", "last_launch", "launch_trace",
     "ACC_FP32",
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
@@ -72,6 +72,30 @@ def last_launch() -> dict:
     return {"kernel": li.kernel.decode(), "grid": li.grid, "block": li.block, "lds_bytes": li.lds_bytes,
             "vgprs": li.regs, "resident_per_cu": li.resident_per_cu, "cus": li.cus,
             "grid_resident": li.grid <= li.resident_per_cu * li.cus}
+
+
+class launch_trace:
+    """with launch_trace() as tr: every kernel this thread launches in the block
+    (allred_launch_trace_begin / _end).  After the block: tr.kernels (the names in
+    launch order, template arguments included, the first 64), tr.grids, tr.blocks
+    and tr.count (all launches seen, stored or not)."""
+
+    def __init__(self):
+        self.kernels, self.grids, self.blocks, self.count = [], [], [], 0
+
+    def __enter__(self):
+        check(lib.allred_launch_trace_begin(), "launch_trace_begin")
+        return self
+
+    def __exit__(self, *exc):
+        rec = (_lib.LaunchRec * _lib.TRACE_CAP)()
+        n = C.c_int(0)
+        check(lib.allred_launch_trace_end(rec, _lib.TRACE_CAP, C.byref(n)), "launch_trace_end")
+        stored = rec[:min(n.value, _lib.TRACE_CAP)]
+        self.kernels = [r.kernel.decode() for r in stored]
+        self.grids = [r.grid for r in stored]
+        self.blocks = [r.block for r in stored]
+        self.count = n.value
 
 
 # ---------------------------------------------------------------- schedule

@@ -118,6 +118,13 @@ class LaunchInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+TRACE_CAP = 64   # records allred_launch_trace_end can return
+
+
+class LaunchRec(C.Structure):   # allred_launch_rec
+    _fields_ = [("kernel", C.c_char * 64), ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+
 class RankCheck(C.Structure):
     _fields_ = [("bad", C.c_uint64), ("first_bad", C.c_uint64), ("max_error", C.c_float), ("reserved", C.c_int32)]
 
@@ -192,6 +199,8 @@ SIGNATURES = [
     ("allred_tune_set", C.c_int, [C.c_char_p, C.c_int64]),
     ("allred_tune_get", C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
     ("allred_last_launch", C.c_int, [C.POINTER(LaunchInfo)]),
+    ("allred_launch_trace_begin", C.c_int, []),
+    ("allred_launch_trace_end", C.c_int, [C.POINTER(LaunchRec), C.c_int, C.POINTER(C.c_int)]),
     ("allred_args_parse", C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Args)]),
     ("allred_run", C.c_int, [C.POINTER(Args), C.c_int, C.POINTER(Report)]),
     ("allred_run_io", C.c_int, [C.POINTER(Args), C.c_int, C.POINTER(Report), _u16p, _u16p, _P]),

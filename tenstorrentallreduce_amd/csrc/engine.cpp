@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1428,7 +1429,31 @@ struct LaunchNote {
     int device = -1;
 };
 thread_local LaunchNote g_last_launch;
+
+// the launch trace of this thread (allred_launch_trace_begin / _end): a fixed ring, no allocation
+constexpr int kTraceCap = 64;
+struct LaunchTrace {
+    uint32_t seen = 0;   // launches since begin, stored or not
+    allred_launch_rec rec[kTraceCap];
+};
+thread_local LaunchTrace g_trace;
 }  // namespace
+
+thread_local bool g_trace_armed = false;
+
+void trace_launch_armed(unsigned grid, unsigned block, const char* fmt, ...) {
+    LaunchTrace& t = g_trace;
+    if (t.seen < (uint32_t)kTraceCap) {
+        allred_launch_rec& r = t.rec[t.seen];
+        va_list ap;
+        va_start(ap, fmt);
+        std::vsnprintf(r.kernel, sizeof(r.kernel), fmt, ap);
+        va_end(ap);
+        r.grid = grid;
+        r.block = block;
+    }
+    ++t.seen;
+}
 
 void note_launch(const void* func, const char* name, unsigned grid, unsigned block) {
     LaunchNote& l = g_last_launch;
@@ -1437,8 +1462,25 @@ void note_launch(const void* func, const char* name, unsigned grid, unsigned blo
     l.grid = grid;
     l.block = block;
     (void)hipGetDevice(&l.device);
+    trace_launch(grid, block, "%s", name);
 }
 }  // namespace tsa
+
+extern "C" int allred_launch_trace_begin(void) {
+    tsa::g_trace.seen = 0;
+    tsa::g_trace_armed = true;
+    return ALLRED_OK;
+}
+
+extern "C" int allred_launch_trace_end(allred_launch_rec* out, int cap, int* count) {
+    if (!count || cap < 0 || (cap > 0 && !out) || !tsa::g_trace_armed) return ALLRED_ERR_ARG;
+    tsa::g_trace_armed = false;
+    const tsa::LaunchTrace& t = tsa::g_trace;
+    const int stored = (int)(t.seen < (uint32_t)tsa::kTraceCap ? t.seen : (uint32_t)tsa::kTraceCap);
+    for (int i = 0; i < stored && i < cap; ++i) out[i] = t.rec[i];
+    *count = (int)t.seen;
+    return ALLRED_OK;
+}
 
 extern "C" int allred_last_launch(allred_launch_info* out) {
     if (!out) return ALLRED_ERR_ARG;

@@ -50,6 +50,17 @@ int64_t tune(Tune key);
 // hierarchical one-launch steps) record the kernel and the grid they chose.
 void note_launch(const void* func, const char* name, unsigned grid, unsigned block);
 
+// ---------------- the launch trace of this thread (allred_launch_trace_begin / _end, engine.cpp) ----------------
+// Every launch site of kernels.hip calls trace_launch with the kernel's name, template arguments
+// included ("k_tree_lds<16, true>"), as a printf format; note_launch feeds it as well.  Disarmed
+// (the normal state) it is one thread-local load and a branch; it never touches allred_last_launch.
+extern thread_local bool g_trace_armed;
+void trace_launch_armed(unsigned grid, unsigned block, const char* fmt, ...);
+template <class... A>
+inline void trace_launch(unsigned grid, unsigned block, const char* fmt, A... args) {
+    if (g_trace_armed) trace_launch_armed(grid, block, fmt, args...);
+}
+
 // ---------------- device launchers (kernels.hip) ----------------
 // All take hipStream_t as void* and return ALLRED_OK / ALLRED_ERR_*.
 int launch_bf16_add(uint16_t* dst, const uint16_t* src, size_t n, void* stream);

@@ -1803,6 +1803,9 @@ int last_error() { return hip_status((int)hipGetLastError()); }
 // fused_form (tune.cpp): 0 auto, 1 register tree, 2 one tile per workgroup, 3 persistent
 inline int64_t fused_form() { return tune(Tune::fused_form); }
 
+// a bool template argument as the launch trace spells it
+constexpr const char* tf(bool b) { return b ? "true" : "false"; }
+
 // The rank count as a template argument: f(std::integral_constant<int, total>{}) for a power of
 // two total in [LO, HI]; false (nothing launched) when the kernels have no instance for it.
 template <int LO, int HI, class F>
@@ -1842,6 +1845,7 @@ int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, c
         found = for_ranks<8, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree_lds_pipe<p(), false>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order,
                                block_vec, span, out, out_stride);
+            trace_launch(grid, kBlock, "k_tree_lds_pipe<%d, false>", total);
         });
     } else if (whole_tiles && form != 1) {   // one tile per workgroup, staged in LDS
         TileSpan span;
@@ -1849,6 +1853,7 @@ int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, c
         found = for_ranks<8, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree_lds<p(), WRITE_ALL>), dim3((unsigned)tiles), dim3(kBlock), 0, st, ranks, stride,
                                order, block_vec, span, out, out_stride);
+            trace_launch((unsigned)tiles, kBlock, "k_tree_lds<%d, %s>", total, tf(WRITE_ALL));
         });
     } else {   // the register form: fewer than 8 ranks, and buckets that are not whole tiles
         const int lanes = total >= 8 ? total / 8 : 1;
@@ -1859,6 +1864,7 @@ int tree_dispatch(uint16_t* ranks, uint64_t stride, uint64_t n_vec, int total, c
         found = for_ranks<1, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree<p(), WRITE_ALL>), dim3((unsigned)blocks), dim3(kBlock), 0, st, ranks, stride,
                                n_vec, order, block_vec, out, out_stride);
+            trace_launch((unsigned)blocks, kBlock, "k_tree<%d, %s>", total, tf(WRITE_ALL));
         });
     }
     return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
@@ -1908,12 +1914,19 @@ int launch_bf16_add(uint16_t* dst, const uint16_t* src, size_t n, void* stream) 
     if (!dst || !src) return ALLRED_ERR_ARG;
     if (aligned16(dst) && aligned16(src)) {
         const uint64_t nv = n / 8;
-        if (nv) hipLaunchKernelGGL(k_add, dim3(grid_all(nv)), dim3(kBlock), 0, st,
-                                   reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), nv);
+        if (nv) {
+            hipLaunchKernelGGL(k_add, dim3(grid_all(nv)), dim3(kBlock), 0, st,
+                               reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), nv);
+            trace_launch(grid_all(nv), kBlock, "k_add");
+        }
         const uint64_t tail = n - nv * 8;
-        if (tail) hipLaunchKernelGGL(k_add_scalar, dim3(1), dim3(64), 0, st, dst + nv * 8, src + nv * 8, tail);
+        if (tail) {
+            hipLaunchKernelGGL(k_add_scalar, dim3(1), dim3(64), 0, st, dst + nv * 8, src + nv * 8, tail);
+            trace_launch(1, 64, "k_add_scalar");
+        }
     } else {
         hipLaunchKernelGGL(k_add_scalar, dim3(grid_for(n)), dim3(kBlock), 0, st, dst, src, (uint64_t)n);
+        trace_launch(grid_for(n), kBlock, "k_add_scalar");
     }
     return last_error();
 }
@@ -1933,6 +1946,7 @@ int launch_bf16_add_segs(uint16_t* dst, const uint16_t* src, const uint64_t* off
     if (!longest) return ALLRED_OK;
     hipLaunchKernelGGL(k_add_segs, dim3(grid_all(longest), nsegs), dim3(kBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), segs);
+    trace_launch(grid_all(longest) * (unsigned)nsegs, kBlock, "k_add_segs");
     return last_error();
 }
 
@@ -1951,6 +1965,7 @@ uint64_t fused_launches(int variant, bool lo_tree, int algo, int side, size_t n,
     const bool big64 = total == 64 && nv % 32 == 0 && bv % 32 == 0 && tiles >= 1024;
     if (variant == ALLRED_MEM) return big64 && fused_form() == 0 ? fused_chunk_launches(tiles) : 1;
     if (variant == ALLRED_LO && !lo_tree) {
+        if (total == 1) return 0;   // launch_butterfly: one rank has nothing to reduce
         if (!tune(Tune::lo_dag_reg) || n % 256 || tiles < (uint64_t)tune(Tune::lo_dag_reg_min_tiles)) return 1;
 #define TSA_X(D, A, S, T) \
     if (algo == (A) && total == (T) && ((A) == ALLRED_SWING_1D || side == (S))) return fused_chunk_launches(tiles);
@@ -2004,6 +2019,7 @@ int launch_tree_fused(uint16_t* ranks, uint64_t stride, size_t n, int total, con
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_tree_lds_pipe<p(), true>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, order, bv,
                                span, nullptr, (uint64_t)0);
+            trace_launch(grid, kBlock, "k_tree_lds_pipe<%d, true>", total);
         });
         if (!found) return ALLRED_ERR_UNSUPPORTED;
         return last_error();
@@ -2023,7 +2039,8 @@ int launch_lo_dag_reg(uint16_t* ranks, uint64_t stride, size_t n, int algo, int 
             TileSpan span;                                                                            \
             tile_span_make(&span, a, b - a, grid, 0);                                                 \
             hipLaunchKernelGGL(k_lo_dag_reg<D>, dim3(grid), dim3(kBlock), 0, st, ranks, stride, span); \
-        });                                                                                           \
+            trace_launch(grid, kBlock, "k_lo_dag_reg<" #D ">");                                        \
+        });                                                                                         \
         return last_error();                                                                          \
     }
     TSA_LO_DAGS(TSA_X)
@@ -2055,11 +2072,13 @@ int launch_butterfly(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
         else
             hipLaunchKernelGGL(k_butterfly_lds64_pipe<0>, grid, dim3(kBlock), 0, st, ranks, stride, d_partner, steps,
                                span, nullptr);
+        trace_launch(grid.x, kBlock, dag ? "k_butterfly_lds64_pipe<4>" : "k_butterfly_lds64_pipe<0>");
         return last_error();
     }
     if (total == 64 && nv % 32 == 0 && tiles >= 256) {  // >= 256 tiles: the LDS-staged form pays
         hipLaunchKernelGGL(k_butterfly_lds64, dim3((unsigned)tiles), dim3(kBlock), 0, st, ranks, stride, d_partner,
                            steps);
+        trace_launch((unsigned)tiles, kBlock, "k_butterfly_lds64");
         return last_error();
     }
     const int Q = 64 / total;
@@ -2074,6 +2093,7 @@ int launch_butterfly(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
     const bool found = for_ranks<2, 64>(total, [&](auto p) {
         if (small) hipLaunchKernelGGL((k_butterfly<p(), 1>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps);
         else hipLaunchKernelGGL((k_butterfly<p(), 8>), grid, blk, 0, st, ranks, stride, nv, d_partner, steps);
+        trace_launch(grid.x, kBlock, "k_butterfly<%d, %d>", total, U);
     });
     if (!found) return ALLRED_ERR_UNSUPPORTED;
     return last_error();
@@ -2129,6 +2149,7 @@ int launch_tree_group(const allred_bucket* buckets, int count, int total, int al
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             if (write_all) hipLaunchKernelGGL((k_tree_group<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span);
             else hipLaunchKernelGGL((k_tree_group<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span);
+            trace_launch(grid, kBlock, "k_tree_group<%d, %s>", total, tf(write_all));
         });
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
     };
@@ -2199,6 +2220,8 @@ int launch_shard_group(const allred_shard_bucket* buckets, int count, int total,
                 hipLaunchKernelGGL((k_tree_group<p(), false, GroupShards>), dim3(grid), dim3(kBlock), 0, st, order, span,
                                    shards);
             else hipLaunchKernelGGL((k_tree_group<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span);
+            if (gather) trace_launch(grid, kBlock, "k_ag_group<%d>", total);
+            else trace_launch(grid, kBlock, with_shards ? "k_tree_group<%d, false, GroupShards>" : "k_tree_group<%d, false>", total);
         });
         shards = GroupShards{};
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
@@ -2253,6 +2276,8 @@ int launch_tree_bcast_x(uint16_t* cur, uint16_t* prev, uint64_t stride, size_t n
                 default: TSA_TBX(1, true); break;
 #undef TSA_TBX
             }
+            trace_launch(grid.x, kBlock, "k_tree_bcast_x<%d, %s>", tune(Tune::tree_bcast_lag) ? 1 : 0,
+                         tf(tune(Tune::tree_bcast_bal) != 0));
         });
         return last_error();
     }
@@ -2265,6 +2290,7 @@ int launch_broadcast(uint16_t* ranks, uint64_t stride, size_t n, int total, cons
     const uint64_t nv = n / 8;
     hipLaunchKernelGGL(k_broadcast, dim3(grid_all(nv), (total + 7) / 8), dim3(kBlock), 0, (hipStream_t)stream, ranks,
                        stride, total, reinterpret_cast<const uint4*>(src), nv);
+    trace_launch(grid_all(nv) * (unsigned)((total + 7) / 8), kBlock, "k_broadcast");
     return last_error();
 }
 
@@ -2284,6 +2310,7 @@ int launch_all_gather(uint16_t* ranks, uint64_t stride, size_t n, int total, con
     const dim3 grid((unsigned)((groups + per - 1) / per));
     hipLaunchKernelGGL(k_ag, grid, dim3(kBlock), 0, (hipStream_t)stream, ranks, stride, total, nv, bv, in, in_stride,
                        chunks, items);
+    trace_launch(grid.x, kBlock, "k_ag");
     return last_error();
 }
 
@@ -2305,6 +2332,7 @@ int launch_bo_steps(uint16_t* ranks, uint64_t stride, int total, int steps, cons
     const unsigned grid = (unsigned)(units < (uint64_t)kMaxGrid ? units : (uint64_t)kMaxGrid);
     hipLaunchKernelGGL(k_bo_steps, dim3(grid), dim3(kBlock), 0, st, ranks, stride, d_tab, total, steps,
                        bv, slices, units, stamps);
+    trace_launch(grid, kBlock, "k_bo_steps");
     return last_error();
 }
 
@@ -2330,6 +2358,7 @@ int launch_lo_steps(uint16_t* ranks, uint64_t stride, int total, int steps, cons
     const unsigned grid = (unsigned)(units < (uint64_t)kMaxGrid ? units : (uint64_t)kMaxGrid);
     hipLaunchKernelGGL(k_lo_steps, dim3(grid), dim3(kBlock), 0, st, ranks, stride, d_pairs, total,
                        steps, nv, units, stamps);
+    trace_launch(grid, kBlock, "k_lo_steps");
     return last_error();
 }
 
@@ -2346,6 +2375,7 @@ static int launch_step(bool add, uint16_t* ranks, uint64_t stride, int total, co
     else
         hipLaunchKernelGGL((k_step_w<false, 8>), g, dim3(64), 0, (hipStream_t)stream, ranks, stride, d_partner,
                            d_blocks, blocks_per_rank, bv);
+    trace_launch(g.x, 64, add ? "k_step_w<true, 8>" : "k_step_w<false, 8>");
     return last_error();
 }
 
@@ -2365,6 +2395,7 @@ int launch_lo_step(const uint16_t* src, uint64_t src_stride, uint16_t* dst, uint
     const uint64_t nv = n / 8;
     hipLaunchKernelGGL(k_lo_step, dim3(grid_all(nv), total), dim3(kBlock), 0, (hipStream_t)stream, src, src_stride,
                        dst, dst_stride, d_partner, nv);
+    trace_launch(grid_all(nv) * (unsigned)total, kBlock, "k_lo_step");
     return last_error();
 }
 
@@ -2374,6 +2405,7 @@ int launch_copy_ranks(const uint16_t* src, uint64_t src_stride, uint16_t* dst, u
     const uint64_t nv = n / 8;
     hipLaunchKernelGGL(k_copy_ranks, dim3(grid_all(nv), total), dim3(kBlock), 0, (hipStream_t)stream, src, src_stride,
                        dst, dst_stride, nv);
+    trace_launch(grid_all(nv) * (unsigned)total, kBlock, "k_copy_ranks");
     return last_error();
 }
 
@@ -2388,6 +2420,7 @@ int launch_validate(const uint16_t* ranks, uint64_t stride, size_t n, int rows, 
     hipLaunchKernelGGL(k_validate, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, ranks, stride, nv, rows,
                        reinterpret_cast<const uint4*>(src0), reinterpret_cast<const uint4*>(src1), mult, error, rne,
                        d_ctr);
+    trace_launch(grid, kBlock, "k_validate");
     return last_error();
 }
 
@@ -2404,6 +2437,7 @@ int mem_reduce_impl(uint16_t* r, uint64_t stride, uint64_t nv, int total, uint16
         const dim3 grid((unsigned)(nv / 32)), blk(128);
         for_ranks<4, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_mem_lds<p(), ACC16>), grid, blk, 0, st, r, stride, bv, dst);
+            trace_launch(grid.x, 128, "k_mem_lds<%d, %s>", total, tf(ACC16));
         });
         return last_error();
     }
@@ -2412,6 +2446,7 @@ int mem_reduce_impl(uint16_t* r, uint64_t stride, uint64_t nv, int total, uint16
     uint64_t g = (nv + kBlock - 1) / kBlock;
     if (g > (uint64_t)kMaxGrid) g = kMaxGrid;
     hipLaunchKernelGGL((k_mem<false, 16, ACC16>), dim3((unsigned)g), dim3(kBlock), 0, st, r, stride, total, nv, bv, dst);
+    trace_launch((unsigned)g, kBlock, "k_mem<false, 16, %s>", tf(ACC16));
     return last_error();
 }
 
@@ -2426,6 +2461,7 @@ int mem_fused_impl(uint16_t* ranks, uint64_t stride, uint64_t nv, int total, hip
             TileSpan span;
             tile_span_make(&span, a, b - a, grid, bv / 32);
             hipLaunchKernelGGL((k_mem_lds_lag<ACC16>), dim3(grid), dim3(kBlock), 0, st, ranks, stride, span);
+            trace_launch(grid, kBlock, "k_mem_lds_lag<%s>", tf(ACC16));
         });
         return last_error();
     }
@@ -2433,11 +2469,13 @@ int mem_fused_impl(uint16_t* ranks, uint64_t stride, uint64_t nv, int total, hip
         const dim3 grid((unsigned)tiles), blk(128);
         const bool found = for_ranks<4, 64>(total, [&](auto p) {
             hipLaunchKernelGGL((k_mem_lds<p(), ACC16>), grid, blk, 0, st, ranks, stride, bv, (uint16_t*)nullptr);
+            trace_launch(grid.x, 128, "k_mem_lds<%d, %s>", total, tf(ACC16));
         });
         if (found) return last_error();
     }
     hipLaunchKernelGGL((k_mem<true, 8, ACC16>), dim3(grid_for(nv)), dim3(kBlock), 0, st, ranks, stride, total, nv, bv,
                        nullptr);
+    trace_launch(grid_for(nv), kBlock, "k_mem<true, 8, %s>", tf(ACC16));
     return last_error();
 }
 }  // namespace
@@ -2465,6 +2503,7 @@ int launch_rows_sum(const uint16_t* rows, uint64_t stride, size_t n, int nrows, 
     else
         hipLaunchKernelGGL((k_mem<false, 16, false>), dim3((unsigned)g), dim3(kBlock), 0, (hipStream_t)stream, r,
                            stride, nrows, nv, nv, dst);
+    trace_launch((unsigned)g, kBlock, "k_mem<false, 16, %s>", tf(acc16));
     return last_error();
 }
 

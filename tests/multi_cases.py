@@ -180,7 +180,15 @@ def rccl_case_expected(world, variant, algo, local, chans, n, data):
     return [np.concatenate(x) for x in tdh.expected(variant, algo, world, local, data, C)]
 
 
-def rccl_mem_inputs(world, acc, n):
+RCCL_MEM_DATASETS = ("soft", "cancel")
+
+
+def rccl_mem_inputs(world, acc, n, dataset="soft"):
+    """soft: the usual [1, 100) range, which an fp32 sum adds exactly in any order; cancel:
+    tests/hard_inputs.py, on which the owner's order of the adds shows in the result bits"""
+    if dataset == "cancel":
+        import hard_inputs
+        return [row.copy() for row in hard_inputs.cancel(world, n, 77 * world + acc)]
     return [np.random.default_rng(77 * world + acc + g).integers(0x3F80, 0x42C8, n).astype(np.uint16)
             for g in range(world)]
 

@@ -317,13 +317,56 @@ def test_tune_table_is_the_product_forms_only():
         assert f" {key} " not in tune_doc, key
 
 
+def test_launch_trace_symbols_and_abi_version():
+    """the trace is an addition: both entry points exported and bound, the ABI still 7"""
+    bound = {n for n, _, _ in _lib.SIGNATURES}
+    for name in ("allred_launch_trace_begin", "allred_launch_trace_end"):
+        assert name in declared_functions() and name in bound and hasattr(_lib.lib, name), name
+    assert _lib.lib.allred_abi_version() == 7
+    assert C.sizeof(_lib.LaunchRec) == 72
+
+
+def test_launch_trace_without_a_launch_is_empty():
+    """begin / end around nothing: count 0, no record written; a host-only call records nothing"""
+    with t.launch_trace() as tr:
+        pass
+    assert (tr.count, tr.kernels, tr.grids) == (0, [], [])
+    with t.launch_trace() as tr:
+        t.schedule(t.SWING, 8, 64)
+    assert tr.count == 0
+    rec = (_lib.LaunchRec * 2)()
+    rec[0].grid = 77
+    n = C.c_int(-1)
+    assert _lib.lib.allred_launch_trace_begin() == 0
+    assert _lib.lib.allred_launch_trace_end(rec, 2, C.byref(n)) == 0
+    assert n.value == 0 and rec[0].grid == 77 and rec[0].kernel == b""
+    # cap 0 with no buffer is a valid way to count
+    assert _lib.lib.allred_launch_trace_begin() == 0
+    assert _lib.lib.allred_launch_trace_end(None, 0, C.byref(n)) == 0 and n.value == 0
+
+
+def test_launch_trace_rejects_bad_arguments():
+    lib, n = _lib.lib, C.c_int(0)
+    rec = (_lib.LaunchRec * 4)()
+    ERR_ARG = -1
+    assert lib.allred_launch_trace_end(rec, 4, C.byref(n)) == ERR_ARG       # end without begin
+    assert lib.allred_launch_trace_begin() == 0
+    assert lib.allred_launch_trace_end(rec, 4, None) == ERR_ARG             # no count
+    assert lib.allred_launch_trace_end(rec, -1, C.byref(n)) == ERR_ARG      # negative cap
+    assert lib.allred_launch_trace_end(None, 4, C.byref(n)) == ERR_ARG      # cap without a buffer
+    assert lib.allred_launch_trace_end(rec, 4, C.byref(n)) == 0             # a rejected end leaves the trace armed
+    assert lib.allred_launch_trace_end(rec, 4, C.byref(n)) == ERR_ARG       # and a good one disarms it
+    with pytest.raises(t.AllredError):
+        t.launch_trace().__exit__(None, None, None)
+
+
 def test_ctypes_structures_match_the_header_layout(tmp_path):
     """Every struct _lib.py mirrors has the header's size and field offsets (a C program
     compiled against include/allred.h prints them): a binding that drops or reorders a
     field — e.g. a PlanDesc without mem_accum — reads past the caller's struct."""
     structs = {"allred_plan_desc": _lib.PlanDesc, "allred_args": _lib.Args, "allred_report": _lib.Report,
                "allred_dist_desc": _lib.DistDesc, "allred_multi_plan": _lib.MultiPlan,
-               "allred_multi_opts": _lib.MultiOpts, "allred_launch_info": _lib.LaunchInfo,
+               "allred_multi_opts": _lib.MultiOpts, "allred_launch_info": _lib.LaunchInfo, "allred_launch_rec": _lib.LaunchRec,
                "allred_seg": _lib.Seg, "allred_schedule": _lib.Schedule}
     lines = []
     for cname, py in structs.items():

@@ -124,22 +124,30 @@ def mem_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_inputs
     import oracle
     import tenstorrentallreduce_amd as t
     dist.init_process_group("gloo", rank=rank, world_size=world)
     side, total = GRIDS[world]
     n = 8 * total * 24
     fails = []
-    for acc in (t.ACC_FP32, t.ACC_BF16):
-        data = inputs(world, 1, n, seed=900 + 10 * world + acc)
-        buf = data[rank][0].copy()
-        scratch = np.zeros(2 * n, dtype=np.uint16)
-        desc = t.dist_desc(t.SWING, t.MEM, side, total, n, mem_accum=acc)
-        t.dist_allreduce_host(desc, rank, buf, scratch, gloo_exchange)
-        want = [d[0].copy() for d in data]
-        oracle.allreduce("mem", 1, side, want, total, acc16=acc == t.ACC_BF16)
-        if not np.array_equal(buf, want[rank]):
-            fails.append((acc, int((buf != want[rank]).sum())))
+    # today's [1, 100) data, on which an fp32 sum is exact in any order, and hard_inputs.cancel,
+    # on which the owner's order (own copy first, then the ranks in order) shows in the bits
+    for kind in ("soft", "cancel"):
+        for acc in (t.ACC_FP32, t.ACC_BF16):
+            if kind == "soft":
+                data = inputs(world, 1, n, seed=900 + 10 * world + acc)
+            else:
+                data = [[row.copy()] for row in hard_inputs.cancel(total, n, 900 + 10 * world + acc)]
+            buf = data[rank][0].copy()
+            scratch = np.zeros(2 * n, dtype=np.uint16)
+            desc = t.dist_desc(t.SWING, t.MEM, side, total, n, mem_accum=acc)
+            t.dist_allreduce_host(desc, rank, buf, scratch, gloo_exchange)
+            want = [d[0].copy() for d in data]
+            oracle.allreduce("mem", 1, side, want, total, acc16=acc == t.ACC_BF16)
+            if not np.array_equal(buf, want[rank]):
+                fails.append((kind, acc, int((buf != want[rank]).sum())))
     st = t.dist_program_stats(t.dist_desc(t.SWING, t.MEM, side, total, n), rank)
     if st != {"steps": 2, "add_launches": 1, "segments": 4 * (world - 1)}:
         fails.append(("stats", st))

@@ -26,6 +26,7 @@ for what the 8-GPU node runs — the reference validates every run
 ALLRED_TEST_REHEARSE=1 runs the peer-window cases with every rank on device 0
 (the harness itself rehearsed on a 1-GPU box); the RCCL cases still skip
 (RCCL refuses two ranks on one device)."""
+import itertools
 import os
 import subprocess
 import sys
@@ -171,10 +172,10 @@ def test_rccl_programs_across_gpus(world):
                 want = mc.rccl_case_expected(world, variant, algo, local, chans, n, data)
                 for g in range(world):
                     assert np.array_equal(got[k][g], want[g]), (variant, algo, local, chans, n, k, g)
-        for acc in (t.ACC_FP32, t.ACC_BF16):
+        for kind, acc in itertools.product(mc.RCCL_MEM_DATASETS, (t.ACC_FP32, t.ACC_BF16)):
             n = 8 * total * 640
             desc = t.dist_desc(t.SWING, t.MEM, side, total, n, mem_accum=acc)
-            data = mc.rccl_mem_inputs(world, acc, n)
+            data = mc.rccl_mem_inputs(world, acc, n, kind)
             got = [None] * world
 
             def mem(g):
@@ -188,7 +189,7 @@ def test_rccl_programs_across_gpus(world):
             _threads(world, mem)
             want = mc.rccl_mem_expected(world, acc, data)
             for g in range(world):
-                assert np.array_equal(got[g], want[g]), ("mem", acc, g)
+                assert np.array_equal(got[g], want[g]), ("mem", kind, acc, g)
     finally:
         for c in comms:
             c.close()

@@ -157,12 +157,16 @@ def test_fused_lds_forms_bit_exact(grid, algo, variant):
 @pytest.mark.parametrize("algo", [t.SWING, t.RECDUB])
 def test_fused_persistent_forms_bit_exact_config2_size(algo, variant):
     """64 ranks x 327,680 bf16 (1280 tiles): the persistent double-buffered
-    fused kernels (k_tree_lds_lag, k_butterfly_lds64_pipe,
-    k_mem_lds_lag) on random bf16, against the oracle."""
+    fused kernels (k_tree_lds_lag — also the rank-uniform RecDub LO —, the Swing
+    LO's register DAG k_lo_dag_reg, k_mem_lds_lag) on random bf16, against the
+    oracle; the launch trace holds the docstring to the routing."""
     side, total, n = 8, 64, 327680
     ranks = rand_ranks(total, n, seed=17 + algo)
-    got = run_plan(algo, {"bo": t.BO, "lo": t.LO, "mem": t.MEM}[variant], side, total, ranks, t.EXEC_FUSED,
-                   stride=t.preferred_rank_stride(n))
+    with t.launch_trace() as trace:
+        got = run_plan(algo, {"bo": t.BO, "lo": t.LO, "mem": t.MEM}[variant], side, total, ranks, t.EXEC_FUSED,
+                       stride=t.preferred_rank_stride(n))
+    assert trace.kernels == [{"bo": "k_tree_lds_lag<64>", "mem": "k_mem_lds_lag<false>",
+                              "lo": "k_lo_dag_reg<LoDag1>" if algo == t.SWING else "k_tree_lds_lag<64>"}[variant]]
     want = [r.copy() for r in ranks]
     oracle.allreduce(variant, algo, side, want, total)
     assert (got == np.stack(want)).all()

@@ -8,6 +8,7 @@ on one device, so those GPU cases could never be rehearsed; with their
 expectations proven here, a red case on the first multi-GPU box points at the
 product, not at the test.  (The reference validates every run:
 allred_helper.hpp:84-96 -> validate_result_vector, allred_helper.cpp:18-120.)"""
+import itertools
 import os
 import socket
 import sys
@@ -64,15 +65,15 @@ def worker(rank, world, port, q, which):
                     want = mc.rccl_case_expected(world, variant, algo, local, chans, n, data)[rank]
                     if not np.array_equal(buf, want):
                         fails.append((variant, algo, local, chans, n, rep, int((buf != want).sum())))
-            for acc in (t.ACC_FP32, t.ACC_BF16):
+            for kind, acc in itertools.product(mc.RCCL_MEM_DATASETS, (t.ACC_FP32, t.ACC_BF16)):
                 n = 8 * total * 640
                 desc = t.dist_desc(t.SWING, t.MEM, side, total, n, mem_accum=acc)
-                data = mc.rccl_mem_inputs(world, acc, n)
+                data = mc.rccl_mem_inputs(world, acc, n, kind)
                 buf = data[rank].copy()
                 host(desc, buf, 1)
                 want = mc.rccl_mem_expected(world, acc, data)[rank]
                 if not np.array_equal(buf, want):
-                    fails.append(("mem", acc, int((buf != want).sum())))
+                    fails.append(("mem", kind, acc, int((buf != want).sum())))
         elif which == "pipelined":   # test_rccl_pipelined_across_gpus: 64 local ranks per GPU, K = 3 buckets
             # (the GPU test's 327,680 elements per rank reduced to 8 x total x 64; the pipelined
             # form's bits per bucket are allred_dist_allreduce's, which the host twin runs)
