@@ -38,6 +38,9 @@ extern "C" {
  * Still ABI 7: allred_shard_bucket and allred_plan_reduce_scatter_shards / allred_plan_all_gather_shards /
  * allred_plan_shards_launches are additions — the grouped reduce-scatter into, and the grouped
  * all-gather from, per-bucket shard buffers.
+ * Still ABI 7: allred_shard_bucket_f32, ALLRED_SHARD_ACCUMULATE and allred_plan_reduce_scatter_shards_f32 /
+ * allred_plan_all_gather_shards_f32 / allred_plan_shards_f32_launches are additions — the same two
+ * calls on fp32 shards: the tree accumulated in fp32, one rounding to bf16 on the way back.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -391,6 +394,62 @@ typedef struct {
 int allred_plan_reduce_scatter_shards(allred_plan* plan, const allred_shard_bucket* buckets, int count, void* stream);
 int allred_plan_all_gather_shards(allred_plan* plan, const allred_shard_bucket* buckets, int count, void* stream);
 int allred_plan_shards_launches(const allred_plan* plan, const allred_shard_bucket* buckets, int count, int op);
+
+/* GROUPED calls on FP32 SHARDS: the same two halves of a sharded step for an optimizer that keeps
+ * fp32 gradient shards and fp32 master parameters — the bf16 calls above would need a cast / scale
+ * / accumulate pass behind the reduce-scatter and a cast pass in front of the all-gather, and their
+ * tree has by then rounded every add to bf16.  Two launches per step, as above.  The accepted plans
+ * are the same (ALLRED_BO with ALLRED_EXEC_FUSED, any BO grid, 2D or 1D algo; anything else:
+ * ALLRED_ERR_UNSUPPORTED); the plan supplies the SCHEDULE only.  blk = elems_per_rank / total.
+ * No reference counterpart, and NOT the reference's arithmetic (which stays the default everywhere
+ * else): nothing here is rounded to bf16 before the shard.
+ *   reduce_scatter_shards_f32  element e of block b of a bucket: s = the sum over the P ranks in
+ *                          the shape of tree b (leaves in tree_order[b] order, level k adds
+ *                          adjacent groups of 2^k leaves), every leaf widened bf16 -> fp32 exactly,
+ *                          every add ONE IEEE fp32 add; v = s * scale, one fp32 multiply (also for
+ *                          scale == 1.0f, where it is exact); shard[b * shard_stride + e] = v, or,
+ *                          with ALLRED_SHARD_ACCUMULATE, = old + v as one fp32 add (never an fma).
+ *                          The rank rows are only read; every byte outside the P blocks of blk
+ *                          floats keeps its bits, the gaps of a wide shard_stride included; without
+ *                          the flag the shard is never read.  A non-finite scale is the caller's
+ *                          arithmetic and is allowed.
+ *   all_gather_shards_f32  block b of EVERY rank row, rank b's included, receives
+ *                          bf16_rne(shard[b * shard_stride + e]): IEEE round to nearest even, +-Inf
+ *                          kept, values above the largest finite bf16 become Inf, a NaN stays a NaN,
+ *                          signed zeros and denormals are not flushed.  The shard is only read and
+ *                          only the n elements of each row are written.
+ * Checks, all before any HIP call (a refused call writes nothing).  ALLRED_ERR_ARG: those of the
+ * grouped shard calls above for the plan, count, buckets and every bucket's ranks / rank_stride /
+ * elems_per_rank, the 2^31 - 1 tile cap included; per bucket shard == NULL (the shard is REQUIRED:
+ * there is no in-place form), shard_stride < blk, shard_stride % 4 != 0, a shard not 16-byte
+ * aligned, address arithmetic that would overflow; flags with a bit other than
+ * ALLRED_SHARD_ACCUMULATE; an `op` other than the two constants.  ALLRED_ERR_UNSUPPORTED, for the
+ * WHOLE list: a bucket that is not whole tiles (total < 8 or elems_per_rank % (256 * total) != 0)
+ * — there is ONE kernel form for fp32 shards and no per-bucket route behind it; a flat optimizer
+ * buffer is padded anyway.  count == 0: ALLRED_OK, nothing launched.
+ * DISJOINTNESS is the rule above with 4-byte shard elements (csrc/shard_f32_ranges.hpp): a
+ * bucket's rank rows are one interval [ranks, ranks + total * rank_stride) of 2-byte elements, its
+ * shard is `total` separate block intervals of blk floats; all pairwise disjoint, else
+ * ALLRED_ERR_ARG — overlapping fp32 blocks, one shard named twice and a shard on a rank row alike.
+ * Routing: EVERY bucket goes through the grouped kernel, at most ALLRED_GROUP_MAX per launch —
+ * k_tree_group_f32 / k_ag_group_f32 (csrc/shard_f32_kernels.hip); the tables travel by value, so
+ * the calls can be captured into a graph.  shards_f32_launches is therefore ceil(count / 64) for
+ * either op.  A 64-rank bucket of >= 1024 tiles stays in the grouped kernel as well: there is no
+ * fp32 form of k_tree_lds_lag, and nobody has measured where one would pay — the bf16 calls'
+ * 1024-tile threshold is NOT inherited here.  fused_form does not apply; pipe_grid caps the grids
+ * like every persistent pass; no new tune keys. */
+typedef struct {
+    uint16_t* ranks;                   /* as allred_bucket: bf16 rank rows */
+    uint64_t  rank_stride;             /* bf16 elements */
+    uint64_t  elems_per_rank;
+    float*    shard;                   /* REQUIRED: block b of this bucket at shard + b * shard_stride */
+    uint64_t  shard_stride;            /* fp32 elements; >= blk, % 4 == 0 */
+} allred_shard_bucket_f32;
+#define ALLRED_SHARD_ACCUMULATE 1      /* flags bit 0: shard += value instead of shard = value */
+int allred_plan_reduce_scatter_shards_f32(allred_plan* plan, const allred_shard_bucket_f32* buckets, int count,
+                                          float scale, int flags, void* stream);
+int allred_plan_all_gather_shards_f32(allred_plan* plan, const allred_shard_bucket_f32* buckets, int count, void* stream);
+int allred_plan_shards_f32_launches(const allred_plan* plan, const allred_shard_bucket_f32* buckets, int count, int op);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

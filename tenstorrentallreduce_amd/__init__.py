@@ -321,6 +321,39 @@ class Plan:
             raise AllredError(st, "plan_shards_launches")
         return st
 
+    @staticmethod
+    def _shard_buckets_f32(buckets):
+        """a sequence of (ranks_ptr, stride, elems_per_rank, shard_ptr, shard_stride) — bf16 rank rows,
+        an fp32 shard, its stride in floats — as an allred_shard_bucket_f32 array (None when empty)"""
+        items = [(int(p), int(s), int(n), int(shard) if shard else None, int(shard_stride))
+                 for p, s, n, shard, shard_stride in buckets]
+        return ((_lib.ShardBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def reduce_scatter_shards_f32(self, buckets, scale: float = 1.0, accumulate: bool = False, stream=None) -> None:
+        """allred_plan_reduce_scatter_shards_f32 (fused BO plans): tree b of every bucket summed in
+        fp32 without intermediate rounding, times scale, stored to — accumulate: added into — the
+        fp32 block at shard_ptr + b * shard_stride floats; the rank rows are only read."""
+        arr, count = self._shard_buckets_f32(buckets)
+        flags = _lib.SHARD_ACCUMULATE if accumulate else 0
+        check(lib.allred_plan_reduce_scatter_shards_f32(self._h, arr, count, float(scale), flags, _stream_ptr(stream)),
+              "plan_reduce_scatter_shards_f32")
+
+    def all_gather_shards_f32(self, buckets, stream=None) -> None:
+        """allred_plan_all_gather_shards_f32: block b of the fp32 shard rounded once to bf16 (RNE)
+        into block b of every rank row, for every bucket of the list; the shards are only read."""
+        arr, count = self._shard_buckets_f32(buckets)
+        check(lib.allred_plan_all_gather_shards_f32(self._h, arr, count, _stream_ptr(stream)),
+              "plan_all_gather_shards_f32")
+
+    def shards_f32_launches(self, buckets, op: int) -> int:
+        """Kernel launches reduce_scatter_shards_f32 (op = OP_REDUCE_SCATTER) or all_gather_shards_f32
+        (OP_ALL_GATHER) would enqueue for the list: one per ALLRED_GROUP_MAX buckets."""
+        arr, count = self._shard_buckets_f32(buckets)
+        st = lib.allred_plan_shards_f32_launches(self._h, arr, count, op)
+        if st < 0:
+            raise AllredError(st, "plan_shards_f32_launches")
+        return st
+
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
         st = np.ascontiguousarray(stamps, dtype=np.uint64)

@@ -144,6 +144,14 @@ class ShardBucket(C.Structure):   # allred_shard_bucket: shard None / 0 = in pla
 OP_REDUCE_SCATTER, OP_ALL_GATHER = 0, 1   # ALLRED_OP_*: allred_plan_shards_launches' op
 
 
+class ShardBucketF32(C.Structure):   # allred_shard_bucket_f32: the shard is required, its stride counts floats
+    _fields_ = [("ranks", C.c_void_p), ("rank_stride", C.c_uint64), ("elems_per_rank", C.c_uint64),
+                ("shard", C.c_void_p), ("shard_stride", C.c_uint64)]
+
+
+SHARD_ACCUMULATE = 1   # ALLRED_SHARD_ACCUMULATE: allred_plan_reduce_scatter_shards_f32's flags bit 0
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -193,6 +201,9 @@ SIGNATURES = [
     ("allred_plan_reduce_scatter_shards", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, _P]),
     ("allred_plan_all_gather_shards", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, _P]),
     ("allred_plan_shards_launches", C.c_int, [_P, C.POINTER(ShardBucket), C.c_int, C.c_int]),
+    ("allred_plan_reduce_scatter_shards_f32", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_float, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_f32", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, _P]),
+    ("allred_plan_shards_f32_launches", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -32,6 +32,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "shard_f32_ranges.hpp"
 #include "shard_ranges.hpp"
 #include "tile_span.hpp"
 
@@ -916,6 +917,47 @@ int shards_run(allred_plan* p, const allred_shard_bucket* buckets, int count, in
     return launch_shard_group(buckets, count, p->total, p->d_order, op, /*dry=*/false, stream);
 }
 
+// The checks of the grouped calls on fp32 shards, all before any HIP call: shards_check's on the
+// op, the plan, the list and every bucket's rank rows (group_check); the fp32 shard's rules — it
+// is required, its stride counts floats —; the disjointness rule in 4-byte shard elements
+// (shard_f32_ranges.hpp), which also refuses address arithmetic that would overflow; then the one
+// kernel form's shape: a list with a bucket that is not whole tiles is ALLRED_ERR_UNSUPPORTED.
+int shards_f32_check(const allred_plan* p, const allred_shard_bucket_f32* buckets, int count, int op, int flags) {
+    if (op != ALLRED_OP_REDUCE_SCATTER && op != ALLRED_OP_ALL_GATHER) return ALLRED_ERR_ARG;
+    if (flags & ~ALLRED_SHARD_ACCUMULATE) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count == 0) return ALLRED_OK;
+    if (!buckets) return ALLRED_ERR_ARG;
+    std::vector<allred_bucket> plain((size_t)count);
+    for (int i = 0; i < count; ++i)
+        plain[(size_t)i] = allred_bucket{buckets[i].ranks, buckets[i].rank_stride, buckets[i].elems_per_rank};
+    const int st = group_check(p, plain.data(), count);
+    if (st != ALLRED_OK) return st;
+    const uint64_t total = (uint64_t)p->total;
+    std::vector<ShardF32Range> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_shard_bucket_f32& b = buckets[i];
+        if (!b.shard || b.shard_stride < b.elems_per_rank / total || b.shard_stride % 4 || (uintptr_t)b.shard % 16)
+            return ALLRED_ERR_ARG;
+        ranges[(size_t)i] = ShardF32Range{b.ranks, b.rank_stride, b.elems_per_rank, b.shard, b.shard_stride};
+    }
+    if (!shard_f32_lists_disjoint(ranges.data(), count, total)) return ALLRED_ERR_ARG;
+    for (int i = 0; i < count; ++i)
+        if (total < 8 || buckets[i].elems_per_rank % (256 * total)) return ALLRED_ERR_UNSUPPORTED;
+    return ALLRED_OK;
+}
+
+int shards_f32_run(allred_plan* p, const allred_shard_bucket_f32* buckets, int count, int op, float scale, int flags,
+                   void* stream) {
+    const int st = shards_f32_check(p, buckets, count, op, flags);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_shard_group_f32(buckets, count, p->total, p->d_order, op, scale, (flags & ALLRED_SHARD_ACCUMULATE) != 0,
+                                  /*dry=*/false, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -932,6 +974,21 @@ int allred_plan_shards_launches(const allred_plan* p, const allred_shard_bucket*
     const int st = shards_check(p, buckets, count, op);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_shard_group(buckets, count, p->total, p->d_order, op, /*dry=*/true, nullptr);
+}
+
+int allred_plan_reduce_scatter_shards_f32(allred_plan* p, const allred_shard_bucket_f32* buckets, int count, float scale,
+                                          int flags, void* stream) {
+    return shards_f32_run(p, buckets, count, ALLRED_OP_REDUCE_SCATTER, scale, flags, stream);
+}
+
+int allred_plan_all_gather_shards_f32(allred_plan* p, const allred_shard_bucket_f32* buckets, int count, void* stream) {
+    return shards_f32_run(p, buckets, count, ALLRED_OP_ALL_GATHER, 1.0f, 0, stream);
+}
+
+int allred_plan_shards_f32_launches(const allred_plan* p, const allred_shard_bucket_f32* buckets, int count, int op) {
+    const int st = shards_f32_check(p, buckets, count, op, 0);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_shard_group_f32(buckets, count, p->total, p->d_order, op, 1.0f, false, /*dry=*/true, nullptr);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -19,6 +19,7 @@
 
 #include "device.hpp"
 #include "group_span.hpp"
+#include "launch_util.hpp"
 #include "tile_span.hpp"
 
 namespace tsa {
@@ -1798,31 +1799,10 @@ __global__ __launch_bounds__(kBlock) void k_validate(const uint16_t* __restrict_
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-int last_error() { return hip_status((int)hipGetLastError()); }
+// last_error, tf, for_ranks and persistent_grid: launch_util.hpp (shared with shard_f32_kernels.hip)
 
 // fused_form (tune.cpp): 0 auto, 1 register tree, 2 one tile per workgroup, 3 persistent
 inline int64_t fused_form() { return tune(Tune::fused_form); }
-
-// a bool template argument as the launch trace spells it
-constexpr const char* tf(bool b) { return b ? "true" : "false"; }
-
-// The rank count as a template argument: f(std::integral_constant<int, total>{}) for a power of
-// two total in [LO, HI]; false (nothing launched) when the kernels have no instance for it.
-template <int LO, int HI, class F>
-bool for_ranks(int total, F&& f) {
-    if (total == LO) {
-        f(std::integral_constant<int, LO>{});
-        return true;
-    }
-    if constexpr (LO < HI) return for_ranks<2 * LO, HI>(total, f);
-    return false;
-}
-
-unsigned persistent_grid(uint64_t tiles, uint64_t dflt) {
-    const int64_t g = tune(Tune::pipe_grid);
-    const uint64_t cap = g > 0 ? (uint64_t)g : dflt;
-    return (unsigned)(tiles < cap ? tiles : cap);
-}
 
 // The BO tree pass by shape class.  WRITE_ALL: the fused pass's forms that launch_tree_fused
 // does not take itself.  One row (!WRITE_ALL): the reduce-scatter (block b to out + b *

@@ -1,0 +1,361 @@
+// shard_f32_kernels.hip — the grouped shard calls on fp32 SHARDS
+// (allred_plan_reduce_scatter_shards_f32 / allred_plan_all_gather_shards_f32,
+// allred.h): the two halves of a sharded training step whose gradient shards
+// and master parameters are fp32, without the cast passes around them.
+//
+//   k_tree_group_f32<P, ACC>   k_tree_group's walk; the BO tree of every tile
+//                              in fp32 with NO intermediate rounding, times
+//                              `scale`, stored to (or added into) the fp32
+//                              shard block of the tile.
+//   k_ag_group_f32<P>          k_ag_group's walk; a tile's 256 floats of the
+//                              shard rounded ONCE to bf16 (pack_rne) and
+//                              written to every rank row.
+//
+// A translation unit of its own: kernels.hip's kernels and launch sites are
+// what tests/route_cases.py tabulates, and the bf16 engine's objects stay what
+// they were (same code, same resources).  The arithmetic here depends on the
+// build's -ffp-contract=off (Makefile, HIPFLAGS): `old + s * scale` must be one
+// fp32 multiply and one fp32 add, never an fma — allred.h states the result as
+// those two operations and the tests compare bits.
+#include <type_traits>
+
+#include "device.hpp"
+#include "group_span.hpp"
+#include "launch_util.hpp"
+
+namespace tsa {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) f32x4 global_f32x4;
+
+// The fp32 shard buffers of a grouped launch: entry i for bucket i of the launch, block b of
+// the bucket at shard + b * stride floats.  64 x 16 bytes by value next to the order pointer,
+// GroupSpan and the scale: 8 + 2064 + 1024 + 4 = 3100 bytes of kernel arguments, inside 4 KiB.
+struct GroupShardF32 {     // 16 bytes
+    float* shard;
+    uint64_t stride;       // floats
+};
+struct GroupShardsF32 {
+    GroupShardF32 s[kGroupMax];   // entries past the last bucket: zero
+};
+static_assert(sizeof(GroupShardF32) == 16 && sizeof(GroupShardsF32) == 16 * kGroupMax, "the kernel-argument layout");
+
+// ---------------------------------------------------------------------------
+// The BO tree in fp32: tree_levels / tree_wave_part / tree_join4 of device.hpp
+// with every node 8 floats instead of 8 bf16 — leaves widened exactly (<< 16),
+// every add one IEEE fp32 add, nothing rounded to bf16.  Same pairing, same
+// operand order (fp32 addition is commutative in every bit but a NaN's payload).
+// ---------------------------------------------------------------------------
+struct F8 {
+    f32x4 a, b;   // elements 0-3 and 4-7 of a 16-byte bf16 vector
+};
+
+__device__ __forceinline__ F8 widen8(uint4 x) {
+    F8 r;
+    r.a = f32x4{lo_f(x.x), hi_f(x.x), lo_f(x.y), hi_f(x.y)};
+    r.b = f32x4{lo_f(x.z), hi_f(x.z), lo_f(x.w), hi_f(x.w)};
+    return r;
+}
+
+__device__ __forceinline__ F8 add8f(const F8& x, const F8& y) { return F8{x.a + y.a, x.b + y.b}; }
+
+template <int N>
+__device__ __forceinline__ void tree_levels_f32(F8 (&x)[N]) {
+#pragma unroll
+    for (int s = 1; s < N; s *= 2)
+#pragma unroll
+        for (int i = 0; i < N; i += 2 * s) x[i] = add8f(x[i], x[i + s]);
+}
+
+// lanes l and l ^ 32 of a wave: lower half's value + upper half's, in both lanes.  gfx950's
+// v_permlane32_swap exchanges the upper 32 lanes of one register with the lower 32 of another: of
+// two copies of x it makes the lower half's values in all 64 lanes and the upper half's in all 64.
+__device__ __forceinline__ float add_halves(float x) {
+#if __has_builtin(__builtin_amdgcn_permlane32_swap)
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+#else
+    return x + __shfl_xor(x, 32);
+#endif
+}
+
+// A wave's share of a tile's tree, as tree_wave_part: this lane's LPL adjacent leaves ord[0 .. LPL)
+// of column c widened and summed in registers, then the level across the wave's two lane halves.
+template <int TV, int LPL>
+__device__ __forceinline__ F8 tree_wave_part_f32(const uint4* tile, const uint8_t* ord, int c) {
+    F8 x[LPL];
+#pragma unroll
+    for (int i = 0; i < LPL; ++i) x[i] = widen8(tile[(int)ord[i] * TV + c]);
+    tree_levels_f32(x);
+    F8 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        r.a[i] = add_halves(x[0].a[i]);
+        r.b[i] = add_halves(x[0].b[i]);
+    }
+    return r;
+}
+
+// the 16 bytes at p by a load the compiler does not count: it would wait vmcnt(0) for its own
+// load — with it the LDS-DMA loads in flight, which it cannot see.  wait_vm<N>() + keep() instead.
+__device__ __forceinline__ f32x4 load16_uncounted(const f32x4* p) {
+    f32x4 v;
+    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(v) : "v"(p) : "memory");
+    return v;
+}
+__device__ __forceinline__ void keep(f32x4& v) { asm volatile("" : "+v"(v)); }   // no use of v may move above this
+
+// ---------------------------------------------------------------------------
+// k_tree_group_f32<P, ACC>: k_tree_group's one-row walk — persistent grid,
+// workgroup g takes tiles g + j * G, a forward-only wave-uniform cursor over
+// GroupSpan, two LDS tile buffers filled by LDS-DMA, the order table staged
+// once, the next tile located before the wait — with the tree in fp32.
+//
+// Lane (q, c) = (lane / 32, lane % 32) of wave w widens its LPL = P / 8 leaves
+// of column c (tree positions RPW w + LPL q ..) and adds them, one
+// v_permlane32_swap level joins the two halves, and the four waves' partials
+// meet in `part`: 32 bytes per column and wave, lane (q, c) writing 16-byte
+// half q.  Wave 0 then joins: lane (q, c) adds half q of column c of the four
+// partials — (p0 + p1) + (p2 + p3) —, multiplies by scale, ACC: adds the old
+// 16 bytes, and stores; the 64 lanes' 16 bytes at (2 c + q) * 16 are the tile's
+// contiguous 1 KiB of floats, ONE store instruction per tile.
+//
+// LDS: 2 x P x 512 (tiles) + 4096 (part) + P x 64 (order): 73,728 bytes at
+// P = 64, two workgroups per CU in the 160 KiB.
+//
+// vmcnt, per wave, in issue order (L: a tile's OPS LDS-DMA loads, S: wave 0's
+// result store, A: ACC's load of the old 16 bytes; waves 1-3 issue L only and
+// wait vmcnt(0) for it, nothing else being in flight):
+//   !ACC  L0 | L1 S0 | L2 S1 | ...      before tile j: L(j) S(j-1) outstanding,
+//         vmcnt(1) leaves S(j-1) in flight (vmcnt(0) at j = 0) — k_tree_group's.
+//   ACC   L0 A0 | L1 S0 A1 | L2 S1 A2 | ...   A(j) goes out right before the
+//         wait for L(j), so its round trip overlaps that wait, the reduction
+//         and the join.  Before tile j: L(j) S(j-1) A(j) outstanding — vmcnt(2)
+//         (vmcnt(1) at j = 0, no store yet).  Before the add: behind A(j) are
+//         L(j+1)'s OPS loads, or nothing after the last tile: vmcnt(OPS) / vmcnt(0).
+// The !ACC instance holds no shard load at all (if constexpr).
+// The shard tile of a workgroup is read (ACC) and written by wave 0 of that
+// workgroup alone, and no other tile of the launch touches it (the lists are
+// block-disjoint: engine.cpp shards_f32_check).
+// ---------------------------------------------------------------------------
+template <int P, bool ACC>
+__global__ __launch_bounds__(kBlock) void k_tree_group_f32(const uint8_t* __restrict__ order, GroupSpan span,
+                                                           GroupShardsF32 shards, float scale) {
+    constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
+    static_assert(OPS >= 1, "P >= 8");
+    __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
+    __shared__ __attribute__((aligned(16))) f32x4 part[4 * TV * 2];
+    __shared__ __attribute__((aligned(16))) uint8_t ord_lds[P * ALLRED_MAX_NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    const uint32_t wbase = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&buf[0][0] + (uint32_t)(RPW * w * TV * 16));
+    struct Tile {
+        uint16_t* ranks;   // the bucket's row 0
+        uint64_t stride;
+        uint64_t v0;       // the tile's first 16-byte vector inside a rank row
+        uint32_t block;
+        f32x4* dst;        // the tile's 1 KiB of the shard
+    };
+    uint32_t cursor = 0;   // wave-uniform: it depends on blockIdx and j only
+    auto locate = [&](int j) {
+        const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
+        Tile t;
+        t.ranks = span.b[gt.bucket].ranks;
+        t.stride = span.b[gt.bucket].stride;
+        t.v0 = (uint64_t)gt.local * TV;
+        t.block = gt.block;
+        t.dst = reinterpret_cast<f32x4*>(shards.s[gt.bucket].shard + (uint64_t)gt.block * shards.s[gt.bucket].stride) +
+                (uint64_t)gt.rem * (2 * TV);
+        return t;
+    };
+    auto issue = [&](const Tile& t, int b) {
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            const int r = RPW * w + RPI * k + q;
+            const uint4* src = reinterpret_cast<const uint4*>(t.ranks + (uint64_t)r * t.stride) + t.v0 + c;
+            lds_dma16(src, wbase + (uint32_t)(b * P * TV * 16 + RPI * k * TV * 16));
+        }
+    };
+    const int mine = (int)group_span_mine(span, blockIdx.x);
+    // the order rows of all P blocks, once, then the first tile's loads
+    for (int i = threadIdx.x; i < P * ALLRED_MAX_NODES / 16; i += kBlock)
+        reinterpret_cast<uint4*>(ord_lds)[i] = reinterpret_cast<const uint4*>(order)[i];
+    __syncthreads();
+    if (mine <= 0) return;
+    Tile cur = locate(0), nxt = cur;
+    issue(cur, 0);
+    for (int j = 0; j < mine; ++j) {
+        if (j + 1 < mine) nxt = locate(j + 1);
+        f32x4 old{};
+        if (w == 0) {
+            if constexpr (ACC) {
+                old = load16_uncounted(cur.dst + (2 * c + q));
+                if (j > 0) wait_vm<2>(); else wait_vm<1>();
+            } else {
+                if (j > 0) wait_vm<1>(); else wait_vm<0>();
+            }
+        } else {
+            wait_vm<0>();
+        }
+        lds_barrier();
+        if (j + 1 < mine) issue(nxt, (j + 1) & 1);
+        const uint4* tile = buf[j & 1];
+        const F8 pw = tree_wave_part_f32<TV, LPL>(tile, ord_lds + cur.block * ALLRED_MAX_NODES + RPW * w + LPL * q, c);
+        part[(w * TV + c) * 2 + q] = q ? pw.b : pw.a;
+        lds_barrier();
+        if (w == 0) {
+            const f32x4 s = (part[(0 * TV + c) * 2 + q] + part[(1 * TV + c) * 2 + q]) +
+                            (part[(2 * TV + c) * 2 + q] + part[(3 * TV + c) * 2 + q]);
+            f32x4 v = s * scale;
+            if constexpr (ACC) {
+                if (j + 1 < mine) wait_vm<OPS>(); else wait_vm<0>();
+                keep(old);
+                v = old + v;
+            }
+            __builtin_nontemporal_store(v, (global_f32x4*)(cur.dst + (2 * c + q)));
+        }
+        cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_ag_group_f32<P>: k_ag_group's walk and store loop from an fp32 shard.  A
+// tile's source is wave-uniform: 1 KiB of floats in ONE block of the shard, at
+// shard + b * stride + rem * 256.  Lane c loads its 32 bytes — the 8 floats of
+// column c — as two 16-byte loads (both lane halves q load the same data),
+// rounds them once to bf16 (pack_rne: IEEE RNE, Inf kept, NaN stays NaN, no
+// flushing) into one uint4 and stores that to its rows r = RPW w + RPI k + q.
+// Every row is written — there is no in-place case — and the shard only read.
+// What keeps the compiler's waits exact is k_ag_group's: unconditional loads and
+// stores, two tiles per trip with registers of their own, tile 0 peeled.  Issue
+// order per wave: L0 L1 S0 L2 S1 L3 S2 ... with L two loads and S OPS stores:
+// behind tile j's loads come tile j - 1's OPS stores and tile j + 1's two loads,
+// so the wait before tile j's stores is vmcnt(OPS + 2) — and that is what the
+// ISA has in the loop, twice, and nothing else (vmcnt(2) before the peeled tile
+// 0, vmcnt(OPS) before an odd last tile; what it took: below and DESIGN.md §13).
+// ---------------------------------------------------------------------------
+template <int P>
+__global__ __launch_bounds__(kBlock) void k_ag_group_f32(GroupSpan span, GroupShardsF32 shards) {
+    constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI;
+    static_assert(OPS >= 1, "P >= 8");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = lane % TV, q = lane / TV;
+    struct Tile {
+        uint16_t* ranks;   // the bucket's row 0
+        uint64_t stride;
+        uint64_t v0;       // the tile's first 16-byte vector inside a rank row
+        const f32x4* src;  // the source tile's first 16 bytes
+    };
+    uint32_t cursor = 0;   // wave-uniform: it depends on blockIdx and j only
+    auto locate = [&](int j) {
+        const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
+        const GroupBucket& e = span.b[gt.bucket];
+        const GroupShardF32& sh = shards.s[gt.bucket];
+        return Tile{e.ranks, e.stride, (uint64_t)gt.local * TV,
+                    reinterpret_cast<const f32x4*>(sh.shard + (uint64_t)gt.block * sh.stride) + (uint64_t)gt.rem * (2 * TV)};
+    };
+    const int mine = (int)group_span_mine(span, blockIdx.x);
+    if (mine <= 0) return;
+    const int last = mine - 1;
+    struct Src {
+        f32x4 a, b;
+    };
+    auto load = [&](const Tile& t) { return Src{t.src[2 * c], t.src[2 * c + 1]}; };
+    auto store = [&](const Tile& t, const Src& x) {
+        // The conversions use the loaded floats, so the wait stands in front of THEM, not of the stores.
+        // Without this barrier the scheduler lifts a conversion above the next tile's loads and the
+        // wait goes with it: vmcnt(OPS), the next tile's loads issued only after this tile's landed.
+        __builtin_amdgcn_sched_barrier(0);
+        const uint4 v = make_uint4(pack_rne(x.a[0], x.a[1]), pack_rne(x.a[2], x.a[3]), pack_rne(x.b[0], x.b[1]),
+                                   pack_rne(x.b[2], x.b[3]));
+#pragma unroll
+        for (int k = 0; k < OPS; ++k) {
+            const uint32_t r = (uint32_t)(RPW * w + RPI * k + q);
+            st_nt(reinterpret_cast<uint4*>(t.ranks + (uint64_t)r * t.stride) + t.v0 + c, v);
+        }
+    };
+    // the "next" tile's loads are unconditional: a workgroup's last tile is loaded once more (an L2 hit)
+    auto at = [&](int j) { return locate(j < last ? j : last); };
+    Tile a = locate(0);
+    Src xa = load(a);
+    Tile b = at(1);
+    Src xb = load(b);
+    store(a, xa);
+    // The odd tile behind the pairs is stored after the loop, not by a break out of its middle: the
+    // structurised break joins the loop's latch, and the compiler, which then sees tile j + 2's
+    // registers as possibly in flight at the loop's head, waits vmcnt(OPS + 1) before it reuses one
+    // as a temporary — tile j + 1's first load drained ahead of tile j + 2's (seen in the ISA).
+    int j = 1;
+    for (; j + 1 < mine; j += 2) {
+        a = at(j + 1);
+        xa = load(a);
+        store(b, xb);   // tile j
+        b = at(j + 2);
+        xb = load(b);
+        store(a, xa);   // tile j + 1
+    }
+    if (j < mine) store(b, xb);   // the last tile of an even count: behind its loads only tile j - 1's stores, vmcnt(OPS)
+}
+// k_ag_group's resident cap (tune pipe_grid caps it lower): 8 four-wave workgroups per CU
+constexpr uint64_t kAgGroupGrid = kMaxGrid;
+
+}  // namespace
+
+// A (checked: engine.cpp shards_f32_check) list of whole-tile buckets with fp32 shards through
+// k_tree_group_f32 (ALLRED_OP_REDUCE_SCATTER) or k_ag_group_f32 (ALLRED_OP_ALL_GATHER), kGroupMax
+// buckets per launch, enqueued when its last member is reached.  EVERY bucket takes this route:
+// there is one kernel form for fp32 shards — a 64-rank bucket of >= 1024 tiles stays here too (no
+// fp32 form of k_tree_lds_lag exists and nobody has measured where one would pay), and fused_form
+// does not apply.  dry: nothing is launched and the number of launches is returned.
+int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, int total, const uint8_t* order, int op,
+                           float scale, bool accumulate, bool dry, void* stream) {
+    const bool gather = op == ALLRED_OP_ALL_GATHER;
+    hipStream_t st = (hipStream_t)stream;
+    GroupIn in[kGroupMax];
+    GroupShardsF32 shards{};
+    int pending = 0, launches = 0;
+    uint64_t pending_tiles = 0;
+    auto flush = [&]() -> int {
+        if (!pending) return ALLRED_OK;
+        ++launches;
+        const int members = pending;
+        const uint64_t tiles = pending_tiles;
+        pending = 0;
+        pending_tiles = 0;
+        if (dry) return ALLRED_OK;
+        // the tree pass on 2 workgroups per CU like every tree pass (LDS-bound); the copy, which
+        // holds no LDS, on up to kAgGroupGrid workgroups like k_ag_group
+        const unsigned grid = persistent_grid(tiles, gather ? kAgGroupGrid : 512);
+        GroupSpan span;
+        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+        const bool found = for_ranks<8, 64>(total, [&](auto p) {
+            if (gather) hipLaunchKernelGGL((k_ag_group_f32<p()>), dim3(grid), dim3(kBlock), 0, st, span, shards);
+            else if (accumulate)
+                hipLaunchKernelGGL((k_tree_group_f32<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span, shards, scale);
+            else hipLaunchKernelGGL((k_tree_group_f32<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span, shards, scale);
+            if (gather) trace_launch(grid, kBlock, "k_ag_group_f32<%d>", total);
+            else trace_launch(grid, kBlock, "k_tree_group_f32<%d, %s>", total, tf(accumulate));
+        });
+        shards = GroupShardsF32{};
+        return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
+    };
+    for (int i = 0; i < count; ++i) {
+        const allred_shard_bucket_f32& b = buckets[i];
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        if (total < 8 || nv % 32 || bv % 32) return ALLRED_ERR_UNSUPPORTED;   // the caller's check, kept next to its use
+        shards.s[pending] = GroupShardF32{b.shard, b.shard_stride};
+        in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
+        pending_tiles += tiles;
+        if (pending == kGroupMax) {
+            const int s = flush();
+            if (s != ALLRED_OK) return s;
+        }
+    }
+    const int s = flush();
+    if (s != ALLRED_OK) return s;
+    return dry ? launches : ALLRED_OK;
+}
+
+}  // namespace tsa
