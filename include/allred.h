@@ -41,6 +41,9 @@ extern "C" {
  * Still ABI 7: allred_shard_bucket_f32, ALLRED_SHARD_ACCUMULATE and allred_plan_reduce_scatter_shards_f32 /
  * allred_plan_all_gather_shards_f32 / allred_plan_shards_f32_launches are additions — the same two
  * calls on fp32 shards: the tree accumulated in fp32, one rounding to bf16 on the way back.
+ * Still ABI 7: allred_plan_reduce_scatter_shards_f32_norm and allred_plan_shards_f32_norm_workspace_bytes
+ * are additions — the fp32 grouped reduce-scatter that also leaves the per-rank squared gradient
+ * norm of what it stored, in the same launch.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -450,6 +453,48 @@ int allred_plan_reduce_scatter_shards_f32(allred_plan* plan, const allred_shard_
                                           float scale, int flags, void* stream);
 int allred_plan_all_gather_shards_f32(allred_plan* plan, const allred_shard_bucket_f32* buckets, int count, void* stream);
 int allred_plan_shards_f32_launches(const allred_plan* plan, const allred_shard_bucket_f32* buckets, int count, int op);
+
+/* The fp32 grouped reduce-scatter WITH THE GRADIENT NORM, in the same launches: what an optimizer
+ * step computes between the reduce-scatter and the all-gather (clipping, the non-finite check)
+ * without reading the shards back.  The SHARDS receive, bit for bit, what
+ * allred_plan_reduce_scatter_shards_f32 gives them for the same arguments; accepted plans, routing,
+ * launches (ceil(count / 64): allred_plan_shards_f32_launches(.., ALLRED_OP_REDUCE_SCATTER)
+ * describes this call too) and graph capturability are unchanged; the rank rows are only read.
+ * The kernels trace as k_tree_group_f32_norm<P, false|true>.
+ *   norm_sq[b], b < total   the sum of the squares of every value this call STORED into block b of
+ *                          every bucket of the list — with ALLRED_SHARD_ACCUMULATE the accumulated
+ *                          old + v — in a fixed order of fp32 operations (never an fma):
+ *     tile partial   a tile is 256 consecutive floats of a block: the 256 squares, one fp32 multiply
+ *                    each, added as a balanced binary tree in element order (level k adds adjacent
+ *                    groups of 2^k).
+ *     per launch     (up to 64 consecutive buckets of the list) S = rank b's tile partials in list
+ *                    order, bucket ascending, tile ascending inside block b;  a_l, l = 0 .. 63, = the
+ *                    left-to-right sum of S[l], S[l + 64], S[l + 128], .. from +0.0f;  R = the balanced
+ *                    binary tree over a_0 .. a_63 in index order (squares are never -0: the padding
+ *                    zeros are exact no-ops).
+ *     across launches  norm_sq[b] = (..(R_0 + R_1) + R_2 ..): launch 0 OVERWRITES — the old contents
+ *                    of norm_sq are never read — and launch k > 0 adds its R to what launch k - 1 left.
+ *   A NaN or +-Inf stored anywhere in rank b's blocks makes norm_sq[b] non-finite (compare by
+ *   class): that is the found-inf signal, there is no separate counter; the other ranks' entries
+ *   stay exact.  Only the `total` floats of norm_sq are written.
+ * WORKSPACE: allred_plan_shards_f32_norm_workspace_bytes returns 64 + 4 T, T = the 256-element
+ * tiles of the whole list counted per rank row (what the 2^31 - 1 cap counts); 0 for arguments the
+ * call would refuse, 64 for count == 0.  The first 64 bytes are the arrival counter: the caller
+ * ZEROES them once after allocation, every launch leaves them zero again (a captured graph replays
+ * without a memset node).  The rest holds one float per tile, each launch its own region; its
+ * contents afterwards are unspecified.  Nothing past the returned size is touched.  ONE WORKSPACE
+ * MUST NOT BE IN FLIGHT ON TWO STREAMS at once (nor in two concurrent graph branches): calls that
+ * share a workspace are ordered by the caller.
+ * Checks, all before any HIP call (a refused call writes nothing): the f32 call's, unchanged, then
+ * ALLRED_ERR_ARG for norm_sq NULL or not 4-byte aligned, norm_ws NULL or not 16-byte aligned, and
+ * [norm_sq, + 4 total) or [norm_ws, + workspace bytes) sharing a byte with each other, with a
+ * bucket's rank-row interval or with a shard block — byte-exact, the rule of
+ * csrc/shard_f32_ranges.hpp, so either may lie in the gap of a wide shard_stride.  count == 0:
+ * ALLRED_OK (after the pointer checks), nothing is launched and norm_sq is NOT written. */
+size_t allred_plan_shards_f32_norm_workspace_bytes(const allred_plan* plan, const allred_shard_bucket_f32* buckets, int count);
+int allred_plan_reduce_scatter_shards_f32_norm(allred_plan* plan, const allred_shard_bucket_f32* buckets, int count,
+                                               float scale, int flags, float* norm_sq /* [total], device */,
+                                               void* norm_ws /* device */, void* stream);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

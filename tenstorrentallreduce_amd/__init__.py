@@ -354,6 +354,25 @@ class Plan:
             raise AllredError(st, "plan_shards_f32_launches")
         return st
 
+    def reduce_scatter_shards_f32_norm(self, buckets, norm_sq_ptr, norm_ws_ptr, scale: float = 1.0,
+                                       accumulate: bool = False, stream=None) -> None:
+        """allred_plan_reduce_scatter_shards_f32_norm: reduce_scatter_shards_f32 — the same shard
+        bits — which also leaves, in the same launches, norm_sq[b] = the sum of the squares of what
+        it stored into block b of every bucket (`total` floats at norm_sq_ptr, device).  norm_ws_ptr:
+        shards_f32_norm_workspace_bytes(buckets) bytes of device memory, 16-byte aligned, the first
+        64 zeroed once by the caller; one workspace is never in flight on two streams."""
+        arr, count = self._shard_buckets_f32(buckets)
+        flags = _lib.SHARD_ACCUMULATE if accumulate else 0
+        check(lib.allred_plan_reduce_scatter_shards_f32_norm(self._h, arr, count, float(scale), flags, int(norm_sq_ptr) or None,
+                                                             int(norm_ws_ptr) or None, _stream_ptr(stream)),
+              "plan_reduce_scatter_shards_f32_norm")
+
+    def shards_f32_norm_workspace_bytes(self, buckets) -> int:
+        """Bytes of the workspace reduce_scatter_shards_f32_norm needs for the list: 64 + 4 per
+        256-element tile of a rank row; 0 for a list the call would refuse."""
+        arr, count = self._shard_buckets_f32(buckets)
+        return int(lib.allred_plan_shards_f32_norm_workspace_bytes(self._h, arr, count))
+
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
         st = np.ascontiguousarray(stamps, dtype=np.uint64)

@@ -204,6 +204,9 @@ SIGNATURES = [
     ("allred_plan_reduce_scatter_shards_f32", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_float, C.c_int, _P]),
     ("allred_plan_all_gather_shards_f32", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, _P]),
     ("allred_plan_shards_f32_launches", C.c_int, [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_int]),
+    ("allred_plan_shards_f32_norm_workspace_bytes", C.c_size_t, [_P, C.POINTER(ShardBucketF32), C.c_int]),
+    ("allred_plan_reduce_scatter_shards_f32_norm", C.c_int,
+     [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_float, C.c_int, _P, _P, _P]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

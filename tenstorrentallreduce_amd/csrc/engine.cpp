@@ -32,6 +32,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "shard_f32_norm_ranges.hpp"
 #include "shard_f32_ranges.hpp"
 #include "shard_ranges.hpp"
 #include "tile_span.hpp"
@@ -958,6 +959,34 @@ int shards_f32_run(allred_plan* p, const allred_shard_bucket_f32* buckets, int c
                                   /*dry=*/false, stream);
 }
 
+// the workspace of allred_plan_reduce_scatter_shards_f32_norm for a (checked) list: the counter's
+// 64 bytes and one float per 256-element tile of a rank row — at most 2^31 - 1 of them (group_check)
+size_t shards_f32_norm_bytes(const allred_shard_bucket_f32* buckets, int count) {
+    uint64_t tiles = 0;
+    for (int i = 0; i < count; ++i) tiles += buckets[i].elems_per_rank / 256;
+    return (size_t)(64 + 4 * tiles);
+}
+
+// The checks of allred_plan_reduce_scatter_shards_f32_norm, all before any HIP call: the fp32
+// call's unchanged, then norm_sq and the workspace — there, aligned, and byte-disjoint from each
+// other, from every rank-row interval and from every shard block (shard_f32_norm_ranges.hpp).
+int shards_f32_norm_check(const allred_plan* p, const allred_shard_bucket_f32* buckets, int count, int flags,
+                          const float* norm_sq, const void* norm_ws) {
+    const int st = shards_f32_check(p, buckets, count, ALLRED_OP_REDUCE_SCATTER, flags);
+    if (st != ALLRED_OK) return st;
+    if (!norm_sq || (uintptr_t)norm_sq % 4 || !norm_ws || (uintptr_t)norm_ws % 16) return ALLRED_ERR_ARG;
+    const uint64_t total = (uint64_t)p->total;
+    std::vector<ShardF32Range> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_shard_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = ShardF32Range{b.ranks, b.rank_stride, b.elems_per_rank, b.shard, b.shard_stride};
+    }
+    return shard_f32_norm_disjoint(ranges.data(), count, total, norm_sq, 4 * total, norm_ws,
+                                   shards_f32_norm_bytes(buckets, count))
+               ? ALLRED_OK
+               : ALLRED_ERR_ARG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -989,6 +1018,21 @@ int allred_plan_shards_f32_launches(const allred_plan* p, const allred_shard_buc
     const int st = shards_f32_check(p, buckets, count, op, 0);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_shard_group_f32(buckets, count, p->total, p->d_order, op, 1.0f, false, /*dry=*/true, nullptr);
+}
+
+size_t allred_plan_shards_f32_norm_workspace_bytes(const allred_plan* p, const allred_shard_bucket_f32* buckets, int count) {
+    if (shards_f32_check(p, buckets, count, ALLRED_OP_REDUCE_SCATTER, 0) != ALLRED_OK) return 0;
+    return shards_f32_norm_bytes(buckets, count);
+}
+
+int allred_plan_reduce_scatter_shards_f32_norm(allred_plan* p, const allred_shard_bucket_f32* buckets, int count, float scale,
+                                               int flags, float* norm_sq, void* norm_ws, void* stream) {
+    const int st = shards_f32_norm_check(p, buckets, count, flags, norm_sq, norm_ws);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_shard_group_f32(buckets, count, p->total, p->d_order, ALLRED_OP_REDUCE_SCATTER, scale,
+                                  (flags & ALLRED_SHARD_ACCUMULATE) != 0, /*dry=*/false, stream, norm_sq, norm_ws);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -107,9 +107,12 @@ int launch_shard_group(const allred_shard_bucket* buckets, int count, int total,
                        void* stream);
 // a list of (checked) whole-tile buckets with fp32 shards (shard_f32_kernels.hip): the tree in fp32, times
 // scale, stored to or (accumulate) added into the shards — k_tree_group_f32 —, or the shards rounded once to
-// bf16 into every rank row — k_ag_group_f32 —, ALLRED_GROUP_MAX buckets per launch.  dry: as above
+// bf16 into every rank row — k_ag_group_f32 —, ALLRED_GROUP_MAX buckets per launch.  dry: as above.
+// norm_sq != nullptr (reduce-scatter): k_tree_group_f32_norm, which also leaves the per-rank squared norm
+// of what it stored in norm_sq[total], through the (checked) workspace norm_ws
 int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, int total, const uint8_t* order, int op,
-                           float scale, bool accumulate, bool dry, void* stream);
+                           float scale, bool accumulate, bool dry, void* stream, float* norm_sq = nullptr,
+                           void* norm_ws = nullptr);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,

@@ -7,6 +7,9 @@
 //                              in fp32 with NO intermediate rounding, times
 //                              `scale`, stored to (or added into) the fp32
 //                              shard block of the tile.
+//   k_tree_group_f32_norm<P, ACC>   the same pass, which also leaves the squared
+//                              norm of what it stored, per rank, in norm_sq
+//                              (allred_plan_reduce_scatter_shards_f32_norm).
 //   k_ag_group_f32<P>          k_ag_group's walk; a tile's 256 floats of the
 //                              shard rounded ONCE to bf16 (pack_rne) and
 //                              written to every rank row.
@@ -40,6 +43,28 @@ struct GroupShardsF32 {
     GroupShardF32 s[kGroupMax];   // entries past the last bucket: zero
 };
 static_assert(sizeof(GroupShardF32) == 16 && sizeof(GroupShardsF32) == 16 * kGroupMax, "the kernel-argument layout");
+
+// What k_tree_group_f32_norm takes on top: two pointers, a tile offset and a launch index.
+constexpr uint32_t kNormCounterBytes = 64;   // the arrival counter's block at the head of the workspace
+struct NormArgs {          // 24 bytes
+    float* norm_sq;        // [P]: launch 0 overwrites it, launch k > 0 adds to what launch k - 1 left
+    void* ws;              // kNormCounterBytes (the counter in the first 4), then one float per tile of the call
+    uint32_t tile_off;     // tiles of the launches before this one: this launch's region of the partials
+    uint32_t launch;       // index of this launch in the call
+};
+static_assert(sizeof(NormArgs) == 24, "the kernel-argument layout");
+static_assert(8 + sizeof(GroupSpan) + sizeof(GroupShardsF32) + 8 + sizeof(NormArgs) < 4096, "kernel arguments stay below 4 KiB");
+typedef __attribute__((address_space(1))) uint32_t global_rw_u32;
+
+// How the finalizer of k_tree_group_f32_norm reads the other workgroups' partials — both are valid
+// forms of the in-launch hand-off (the partials are written through and drained before the ticket):
+//   0  one lane's agent-scope acquire fence before the barrier, then plain vector loads;
+//   1  no fence, EVERY load of a partial an agent-scope atomic load (sc1: past this CU's L1).
+// A build-time switch for the A/B of DESIGN.md §14, not a tune key; the default is the form measured faster.
+#ifndef ALLRED_NORM_SC1_LOADS
+#define ALLRED_NORM_SC1_LOADS 0
+#endif
+constexpr bool kNormSc1Loads = ALLRED_NORM_SC1_LOADS != 0;
 
 // ---------------------------------------------------------------------------
 // The BO tree in fp32: tree_levels / tree_wave_part / tree_join4 of device.hpp
@@ -80,6 +105,24 @@ __device__ __forceinline__ float add_halves(float x) {
 #endif
 }
 
+// x + the x of the lane a DPP control names: a register move, no trip through the LDS crossbar
+template <int CTRL>
+__device__ __forceinline__ float add_dpp(float x) {
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
+}
+
+// Five levels of a balanced tree over the 32 lanes of each wave half, in lane order (level k adds
+// adjacent groups of 2^k lanes), as a butterfly: every lane ends with its half's sum.  An fp32 add
+// is commutative, so which of the two siblings a lane reads first does not show in the bits.
+// Every lane of the wave must be active.
+__device__ __forceinline__ float add_lanes32(float t) {
+    t = add_dpp<0xB1>(t);    // quad_perm [1, 0, 3, 2]: lane ^ 1
+    t = add_dpp<0x4E>(t);    // quad_perm [2, 3, 0, 1]: lane ^ 2
+    t = add_dpp<0x141>(t);   // row_half_mirror: a lane of the other quad of the 8, all four of which hold that quad's sum
+    t = add_dpp<0x140>(t);   // row_mirror: likewise the other 8 of the 16
+    return t + __shfl_xor(t, 16);
+}
+
 // A wave's share of a tile's tree, as tree_wave_part: this lane's LPL adjacent leaves ord[0 .. LPL)
 // of column c widened and summed in registers, then the level across the wave's two lane halves.
 template <int TV, int LPL>
@@ -105,6 +148,76 @@ __device__ __forceinline__ f32x4 load16_uncounted(const f32x4* p) {
     return v;
 }
 __device__ __forceinline__ void keep(f32x4& v) { asm volatile("" : "+v"(v)); }   // no use of v may move above this
+
+__device__ __forceinline__ const NormArgs& norm_args(const NormArgs& na) { return na; }   // the one member of the kernel's pack
+
+// NORM: the end of a workgroup's walk — the ticket, and for the last arriver the per-rank sums.
+// ticket: 4 bytes of LDS that only wave 0 has used (`part`: it is done with it); tb: 512 bytes of LDS
+// free once every wave is past its last tile (the tile buffers).
+template <int P>
+__device__ __forceinline__ void norm_finish(const NormArgs& na, const GroupSpan& span, uint32_t* ticket, uint2* tb, int lane,
+                                            int w) {
+    global_rw_u32* counter = (global_rw_u32*)na.ws;
+    // thread t's entry of the finalizer's table, asked for ahead of the ticket (wave 0 holds all 64): its
+    // round trip hides behind the drain instead of standing in the finalizer's serial path
+    uint2 entry{};
+    if (threadIdx.x < kGroupMax) entry = make_uint2(span.b[threadIdx.x].first, span.b[threadIdx.x].tpb);
+    asm volatile("" : "+v"(entry.x), "+v"(entry.y));   // not to be sunk to its use behind the barriers
+    if (w == 0) {
+        wait_vm<0>();   // the storing wave's partials are written through
+        if (lane == 0) {
+            const uint32_t t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!kNormSc1Loads && t == span.G - 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            *ticket = t;
+        }
+        wait_vm<0>();   // the invalidate has happened before the barrier lets the readers go
+    }
+    __syncthreads();
+    if (*ticket != span.G - 1) return;
+    // every wave is past its last tile and no LDS-DMA is in flight: the tile buffers hold the
+    // launch's (first tile, tiles per block) table for the lane-divergent walk below
+    if (threadIdx.x < kGroupMax) tb[threadIdx.x] = entry;
+    __syncthreads();
+    constexpr int RW = P / 4;             // ranks of this wave: w + 4 r
+    const uint32_t L = span.T / P;        // partials per rank: every bucket is P blocks of tpb tiles
+    const float* partials = reinterpret_cast<const float*>(static_cast<const char*>(na.ws) + kNormCounterBytes) + na.tile_off;
+    float a[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) a[r] = 0.0f;
+    uint32_t k = 0, base = 0;             // this lane's cursor: bucket k holds partials [base, base + tpb) of a rank
+    for (uint32_t m0 = 0; m0 < L; m0 += 64) {
+        const uint32_t m = m0 + (uint32_t)lane;
+        if (m < L) {
+            uint2 e = tb[k];
+            while (m - base >= e.y) {
+                base += e.y;
+                e = tb[++k];
+            }
+            const float* at = partials + e.x + (m - base);
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const float* p = at + (uint32_t)(w + 4 * r) * e.y;
+                if constexpr (kNormSc1Loads)
+                    a[r] = a[r] + __uint_as_float(__hip_atomic_load((global_rw_u32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                else
+                    a[r] = a[r] + *p;
+            }
+        }
+    }
+    float out = 0.0f;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        float t = a[r];
+        t = add_halves(add_lanes32(t));
+        if (lane == r) out = t;
+    }
+    if (lane < RW) {
+        float* dst = na.norm_sq + (w + 4 * lane);
+        if (na.launch > 0) out = *dst + out;
+        *dst = out;
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // ---------------------------------------------------------------------------
 // k_tree_group_f32<P, ACC>: k_tree_group's one-row walk — persistent grid,
@@ -138,10 +251,45 @@ __device__ __forceinline__ void keep(f32x4& v) { asm volatile("" : "+v"(v)); }  
 // The shard tile of a workgroup is read (ACC) and written by wave 0 of that
 // workgroup alone, and no other tile of the launch touches it (the lists are
 // block-disjoint: engine.cpp shards_f32_check).
+//
+// NORM (k_tree_group_f32_norm; the other instances hold none of this: if
+// constexpr): norm_sq[b] = the sum of the squares of every float v this launch
+// stores into block b, in the fixed order allred.h states.
+//   per tile   wave 0, which holds v: lane (q, c) has elements 4 (2 c + q) .. + 3
+//              of the tile, so (x0^2 + x1^2) + (x2^2 + x3^2), then the level across
+//              q (add_halves), then c bit 0 .. bit 4 by butterfly — the balanced
+//              tree over the 256 squares in element order.  Lane 0 stores the
+//              partial N to ws_partials[tile_off + global tile] by a relaxed
+//              agent-scope atomic store: ONE write-through (sc1) vector store of 4
+//              bytes, behind S in issue order.  vmcnt with N:
+//   !ACC  L0 | L1 S0 N0 | L2 S1 N1 | ...   before tile j: L(j) S(j-1) N(j-1)
+//         outstanding — vmcnt(2) leaves both stores in flight (vmcnt(0) at j = 0).
+//   ACC   L0 A0 | L1 S0 N0 A1 | L2 S1 N1 A2 | ...   before tile j: L(j) S(j-1)
+//         N(j-1) A(j) — vmcnt(3) (vmcnt(1) at j = 0).  Before the add nothing
+//         changes: behind A(j) are L(j+1)'s OPS loads, or nothing.
+//   at the end of the walk (the in-launch ticket reducer: a counter instead of a
+//   flag, partials written through and drained, so no release fence): wave 0
+//   waits vmcnt(0), lane 0 takes a ticket (relaxed agent-scope fetch_add on the
+//   counter at the head of the workspace) — EVERY workgroup of the grid does, one
+//   without tiles too.  The workgroup that draws G - 1 is the finalizer: that
+//   lane's agent-scope acquire fence, vmcnt(0), __syncthreads(), then plain VECTOR
+//   loads of the partials by all four waves.  Wave w takes ranks w, w + 4, ...:
+//   rank b's partials in list order are, bucket by bucket, the tpb consecutive
+//   floats of block b; lane l adds S[l], S[l + 64], ... from +0.0f, a 64-lane
+//   butterfly is the tree over a_0 .. a_63, one lane adds what the previous
+//   launch left in norm_sq[b] (launch > 0) and stores.  Thread 0 then puts the
+//   counter back to 0 (agent-scope atomic store): the next launch, or replay,
+//   finds it zero.  Nobody waits for another workgroup anywhere.
+// ONE template for both: the pack Norm is empty (k_tree_group_f32<P, ACC>: the
+// arguments and, instruction for instruction, the code of before) or NormArgs
+// (k_tree_group_f32_norm<P, ACC>).  A bool on a shared __device__ body under
+// two __global__ wrappers did not keep the old instances' code.
 // ---------------------------------------------------------------------------
-template <int P, bool ACC>
+template <int P, bool ACC, class... Norm>
 __global__ __launch_bounds__(kBlock) void k_tree_group_f32(const uint8_t* __restrict__ order, GroupSpan span,
-                                                           GroupShardsF32 shards, float scale) {
+                                                           GroupShardsF32 shards, float scale, Norm... norm) {
+    constexpr bool NORM = sizeof...(Norm) == 1;
+    static_assert(sizeof...(Norm) <= 1 && (std::is_same_v<Norm, NormArgs> && ...), "Norm: nothing, or NormArgs");
     constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI, LPL = OPS;
     static_assert(OPS >= 1, "P >= 8");
     __shared__ __attribute__((aligned(16))) uint4 buf[2][P * TV];
@@ -183,18 +331,22 @@ __global__ __launch_bounds__(kBlock) void k_tree_group_f32(const uint8_t* __rest
     for (int i = threadIdx.x; i < P * ALLRED_MAX_NODES / 16; i += kBlock)
         reinterpret_cast<uint4*>(ord_lds)[i] = reinterpret_cast<const uint4*>(order)[i];
     __syncthreads();
-    if (mine <= 0) return;
+    if (mine <= 0) {
+        if constexpr (NORM) norm_finish<P>(norm_args(norm...), span, reinterpret_cast<uint32_t*>(&part[0]), reinterpret_cast<uint2*>(&buf[0][0]), lane, w);
+        return;
+    }
     Tile cur = locate(0), nxt = cur;
     issue(cur, 0);
     for (int j = 0; j < mine; ++j) {
         if (j + 1 < mine) nxt = locate(j + 1);
         f32x4 old{};
         if (w == 0) {
+            constexpr int N = NORM ? 1 : 0;   // the partial's store, in flight behind S
             if constexpr (ACC) {
                 old = load16_uncounted(cur.dst + (2 * c + q));
-                if (j > 0) wait_vm<2>(); else wait_vm<1>();
+                if (j > 0) wait_vm<2 + N>(); else wait_vm<1>();
             } else {
-                if (j > 0) wait_vm<1>(); else wait_vm<0>();
+                if (j > 0) wait_vm<1 + N>(); else wait_vm<0>();
             }
         } else {
             wait_vm<0>();
@@ -215,10 +367,24 @@ __global__ __launch_bounds__(kBlock) void k_tree_group_f32(const uint8_t* __rest
                 v = old + v;
             }
             __builtin_nontemporal_store(v, (global_f32x4*)(cur.dst + (2 * c + q)));
+            if constexpr (NORM) {
+                const NormArgs& na = norm_args(norm...);
+                const f32x4 sq = v * v;
+                float t = (sq[0] + sq[1]) + (sq[2] + sq[3]);
+                t = add_lanes32(add_halves(t));
+                if (lane == 0)
+                    __hip_atomic_store((global_rw_u32*)(static_cast<char*>(na.ws) + kNormCounterBytes) + (na.tile_off + group_span_tile(span, blockIdx.x, (uint32_t)j)),
+                                       __float_as_uint(t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         cur = nxt;
     }
+    if constexpr (NORM) norm_finish<P>(norm_args(norm...), span, reinterpret_cast<uint32_t*>(&part[0]), reinterpret_cast<uint2*>(&buf[0][0]), lane, w);
 }
+
+// the instances with the norm: k_tree_group_f32<P, ACC, NormArgs>, traced as k_tree_group_f32_norm<P, ACC>
+template <int P, bool ACC>
+constexpr auto k_tree_group_f32_norm = k_tree_group_f32<P, ACC, NormArgs>;
 
 // ---------------------------------------------------------------------------
 // k_ag_group_f32<P>: k_ag_group's walk and store loop from an fp32 shard.  A
@@ -309,14 +475,17 @@ constexpr uint64_t kAgGroupGrid = kMaxGrid;
 // there is one kernel form for fp32 shards — a 64-rank bucket of >= 1024 tiles stays here too (no
 // fp32 form of k_tree_lds_lag exists and nobody has measured where one would pay), and fused_form
 // does not apply.  dry: nothing is launched and the number of launches is returned.
+// norm_sq != nullptr (reduce-scatter only): the same launches as k_tree_group_f32_norm, launch k
+// with the partials' region behind the tiles of launches 0 .. k - 1 of norm_ws.
 int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, int total, const uint8_t* order, int op,
-                           float scale, bool accumulate, bool dry, void* stream) {
+                           float scale, bool accumulate, bool dry, void* stream, float* norm_sq, void* norm_ws) {
     const bool gather = op == ALLRED_OP_ALL_GATHER;
+    if (gather && norm_sq) return ALLRED_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     GroupIn in[kGroupMax];
     GroupShardsF32 shards{};
     int pending = 0, launches = 0;
-    uint64_t pending_tiles = 0;
+    uint64_t pending_tiles = 0, launched_tiles = 0;
     auto flush = [&]() -> int {
         if (!pending) return ALLRED_OK;
         ++launches;
@@ -330,7 +499,17 @@ int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, in
         const unsigned grid = persistent_grid(tiles, gather ? kAgGroupGrid : 512);
         GroupSpan span;
         if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+        const NormArgs na{norm_sq, norm_ws, (uint32_t)launched_tiles, (uint32_t)(launches - 1)};
+        launched_tiles += tiles;   // the list's tiles are below 2^31 (engine.cpp group_check)
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
+            if (norm_sq) {
+                if (accumulate)
+                    hipLaunchKernelGGL((k_tree_group_f32_norm<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span, shards, scale, na);
+                else
+                    hipLaunchKernelGGL((k_tree_group_f32_norm<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span, shards, scale, na);
+                trace_launch(grid, kBlock, "k_tree_group_f32_norm<%d, %s>", total, tf(accumulate));
+                return;
+            }
             if (gather) hipLaunchKernelGGL((k_ag_group_f32<p()>), dim3(grid), dim3(kBlock), 0, st, span, shards);
             else if (accumulate)
                 hipLaunchKernelGGL((k_tree_group_f32<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span, shards, scale);
