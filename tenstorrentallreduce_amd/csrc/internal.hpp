@@ -51,9 +51,10 @@ int64_t tune(Tune key);
 void note_launch(const void* func, const char* name, unsigned grid, unsigned block);
 
 // ---------------- the launch trace of this thread (allred_launch_trace_begin / _end, engine.cpp) ----------------
-// Every launch site of kernels.hip calls trace_launch with the kernel's name, template arguments
-// included ("k_tree_lds<16, true>"), as a printf format; note_launch feeds it as well.  Disarmed
-// (the normal state) it is one thread-local load and a branch; it never touches allred_last_launch.
+// Every launch site of kernels.hip and peer_kernels.hip calls trace_launch with the kernel's name,
+// template arguments included ("k_tree_lds<16, true>"), as a printf format; note_launch feeds it as
+// well.  Disarmed (the normal state) it is one thread-local load and a branch; it never touches
+// allred_last_launch.
 extern thread_local bool g_trace_armed;
 void trace_launch_armed(unsigned grid, unsigned block, const char* fmt, ...);
 template <class... A>

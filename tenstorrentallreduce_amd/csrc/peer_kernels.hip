@@ -1214,12 +1214,16 @@ int launch_peer_allreduce(uint16_t* const* wins, uint32_t* const* flags, int nra
     if (rc != ALLRED_OK) return rc;
     // 2. everyone's window is written
     hipLaunchKernelGGL(k_peer_barrier, dim3(1), dim3(64), 0, st, pp, nranks, me, epoch, status);
+    trace_launch(1, 64, "k_peer_barrier");
     // 3. reduce my block from every window
     hipLaunchKernelGGL(k_peer_rs, dim3(grid_all(bv)), dim3(kBlock), 0, st, pp, nranks, me, bucket, bv);
+    trace_launch(grid_all(bv), kBlock, "k_peer_rs");
     // 4. every block is reduced
     hipLaunchKernelGGL(k_peer_barrier, dim3(1), dim3(64), 0, st, pp, nranks, me, epoch + 1, status);
+    trace_launch(1, 64, "k_peer_barrier");
     // 5. gather the other blocks
     hipLaunchKernelGGL(k_peer_ag, dim3(grid_all(bv), nranks), dim3(kBlock), 0, st, pp, me, bucket, bv);
+    trace_launch(grid_all(bv) * (unsigned)nranks, kBlock, "k_peer_ag");
     return peer_last_error();
 }
 
@@ -1228,6 +1232,7 @@ int launch_peer_barrier(uint32_t* const* flags, int nranks, int me, uint32_t epo
     PeerPtrs pp{};
     for (int q = 0; q < nranks; ++q) pp.flags[q] = flags[q];
     hipLaunchKernelGGL(k_peer_barrier, dim3(1), dim3(64), 0, (hipStream_t)stream, pp, nranks, me, epoch, status);
+    trace_launch(1, 64, "k_peer_barrier");
     return peer_last_error();
 }
 
@@ -1259,6 +1264,7 @@ int launch_peer_sched(uint16_t* const* wins, uint32_t* const* flags, int me, uin
     pf.fence = (int)tune(Tune::peer_fence);
     hipLaunchKernelGGL(k_peer_sched, dim3((unsigned)(gc * prog.C)), dim3(kBlock), 0, (hipStream_t)stream, pp, pf, me,
                        bucket, half_vec, base_epoch, status);
+    trace_launch((unsigned)(gc * prog.C), kBlock, "k_peer_sched");
     return peer_last_error();
 }
 
@@ -1288,6 +1294,7 @@ int launch_peer_sched_push(uint16_t* const* wins, uint16_t* const* stages, uint3
     pf.fence = (int)tune(Tune::peer_fence);
     hipLaunchKernelGGL(k_peer_sched_push, dim3((unsigned)(gc * prog.C)), dim3(kBlock), 0, (hipStream_t)stream, pp, ps,
                        pf, me, bucket, base_epoch, status);
+    trace_launch((unsigned)(gc * prog.C), kBlock, "k_peer_sched_push");
     return peer_last_error();
 }
 
@@ -1305,6 +1312,7 @@ int launch_peer_mem_ll(uint64_t* const* ll, int nranks, int me, uint16_t* bucket
     if (groups > cap) groups = cap;   // resident: every wait is reached
     hipLaunchKernelGGL(k_peer_mem_ll, dim3((unsigned)groups), dim3(kBlock), 0, (hipStream_t)stream, lp, nranks, me,
                        bucket, nv, nv / nranks, epoch, status);
+    trace_launch((unsigned)groups, kBlock, "k_peer_mem_ll");
     return peer_last_error();
 }
 
@@ -1318,6 +1326,7 @@ int launch_peer_lo_ll(uint64_t* const* ll, int nranks, int me, uint16_t* bucket,
     for (int q = 0; q < nranks; ++q) lp.ll[q] = ll[q];
     hipLaunchKernelGGL(k_peer_lo_ll, dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, lp, prog, me, bucket, nv, epoch, status);
+    trace_launch((unsigned)((nv + kBlock - 1) / kBlock), kBlock, "k_peer_lo_ll");
     return peer_last_error();
 }
 
@@ -1376,7 +1385,10 @@ int launch_hier_x2(uint16_t* cur, uint16_t* old, uint16_t* fin, uint64_t stride,
     decltype(&k_hier_x2<false>) kern = ch ? k_hier_x2<true> : k_hier_x2<false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, cur, old, fin, stride, order, lc, lm, lo, nranks, me, ntiles, ntiles / nranks,
                        box_words, ecur, emid, eold, llm ? 1 : 0, status);
-    if (cur) note_launch(reinterpret_cast<const void*>(kern), ch ? "k_hier_x2<chunked>" : "k_hier_x2", grid, kBlock);
+    if (cur)
+        note_launch(reinterpret_cast<const void*>(kern), ch ? "k_hier_x2<chunked>" : "k_hier_x2", grid, kBlock);
+    else   // the flush: in the trace, not in allred_last_launch (which keeps the last bucket's launch)
+        trace_launch(grid, kBlock, ch ? "k_hier_x2<chunked>" : "k_hier_x2");
     return peer_last_error();
 }
 
@@ -1397,6 +1409,7 @@ int launch_peer_oneshot(uint16_t* const* wins, uint32_t* const* flags, int nrank
     const uint64_t chunk = (bv + groups - 1) / groups;
     hipLaunchKernelGGL(k_peer_oneshot, dim3((unsigned)groups), dim3(kBlock), 0, (hipStream_t)stream, pp, nranks, me,
                        bucket, bv, chunk, epoch, status, (uint32_t)tune(Tune::peer_fence));
+    trace_launch((unsigned)groups, kBlock, "k_peer_oneshot");
     return peer_last_error();
 }
 

@@ -20,6 +20,8 @@ for what the 8-GPU node runs — the reference validates every run
   tests/test_gpu_peer.py's workers, also with tune peer_fence=1 (a release
   fence before every flag or LL hand-off store, an acquire fence after every
   wait: the same bits);
+- the peer route table (tests/peer_cases.py) on the hard inputs, every case
+  with its launch trace (tests/test_gpu_peer_hard.py's worker);
 - BASELINE config 4 (8-rank Swing BO, 1 GiB per GPU; at G = 2 / 4 on the
   smaller grids) by exact sums of small integers (every reduction order is
   exact), over RCCL and the peer windows (pull and push forms).
@@ -273,6 +275,15 @@ def test_peer_flat_programs_under_launch_skew_across_gpus(world, tunes):
     one-shot, LL) and the scheduled BO / LO programs (pull, push, LL) with random spins ahead of
     every call, bit-exact."""
     tgp.run_world(tgp.skew_flat_worker, world, 300, devs=devices(world), tunes=tunes)
+
+
+@pytest.mark.parametrize("world", WORLDS)
+def test_peer_table_on_hard_inputs_across_gpus(world):
+    """tests/test_gpu_peer_hard.py's table_worker with one process per device: every route of
+    tests/peer_cases.py on the cancel / nonfinite inputs, whole buffers between sentinel guards,
+    the launch trace of every case (the owner-first add order shows from three GPUs on)."""
+    import test_gpu_peer_hard as tgh
+    tgp.run_world(tgh.table_worker, world, 300, devs=devices(world))
 
 
 @pytest.mark.parametrize("tunes", FENCES, ids=["relaxed", "fenced"])
