@@ -44,6 +44,9 @@ extern "C" {
  * Still ABI 7: allred_plan_reduce_scatter_shards_f32_norm and allred_plan_shards_f32_norm_workspace_bytes
  * are additions — the fp32 grouped reduce-scatter that also leaves the per-rank squared gradient
  * norm of what it stored, in the same launch.
+ * Still ABI 7: allred_adamw_bucket_f32, allred_adamw_hyper, ALLRED_ADAMW_GROUP_MAX, ALLRED_ADAMW_ZERO_GRAD and
+ * allred_plan_adamw_all_gather_shards_f32 / allred_plan_adamw_shards_f32_launches are additions — the
+ * clipped AdamW step on the fp32 shards inside the grouped all-gather's launch.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -495,6 +498,85 @@ size_t allred_plan_shards_f32_norm_workspace_bytes(const allred_plan* plan, cons
 int allred_plan_reduce_scatter_shards_f32_norm(allred_plan* plan, const allred_shard_bucket_f32* buckets, int count,
                                                float scale, int flags, float* norm_sq /* [total], device */,
                                                void* norm_ws /* device */, void* stream);
+
+/* ADAMW ON THE FP32 SHARDS, INSIDE THE GROUPED ALL-GATHER'S LAUNCH: what runs between
+ * allred_plan_reduce_scatter_shards_f32_norm and allred_plan_all_gather_shards_f32 — gradient
+ * clipping by the global norm, the non-finite check, torch's non-amsgrad AdamW — at the point where
+ * the all-gather holds every master parameter in a register anyway.  A sharded step is then TWO
+ * launches: the reduce-scatter with the norm, and this call; both can be captured into one graph.
+ * Accepted plans, the rank rows and blk = elems_per_rank / total are those of the fp32 calls above.
+ * The kernel traces as k_adamw_ag_group_f32<P, false|true> (csrc/adamw_kernels.hip; the bool: the
+ * flag below).  No reference counterpart.
+ * HYPERPARAMETERS come through a DEVICE pointer (32 bytes, 16-byte aligned, only read): lr and the
+ * two bias corrections change every step, and by-value arguments would be frozen into a captured
+ * graph — the caller rewrites the 32 bytes with any stream-ordered copy between replays.
+ * SEMANTICS.  Every operation below is ONE IEEE fp32 operation in the order written, never an fma;
+ * division and square root are correctly rounded; denormals are kept.
+ * Uniform values, the same for every element and every launch of the call (P = total):
+ *   N    the balanced binary tree, in index order, over 64 values x_l (level k adds adjacent groups
+ *        of 2^k): x_l = norm_sq[l] for l < P, +0.0f for l >= P.  norm_sq == NULL: N = +0.0f,
+ *        c = 1.0f and skip is false.
+ *   skip = N is NaN or +-Inf: the found-inf signal of allred_plan_reduce_scatter_shards_f32_norm.
+ *   q = max_norm / (sqrtf(N) + 1e-6f);   c = (q < 1.0f) ? q : 1.0f   (max_norm = +Inf: no clipping)
+ *   d = 1.0f - lr * weight_decay;   o1 = 1.0f - beta1;   o2 = 1.0f - beta2;   ss = lr / bias_corr1
+ * Per element e of block b of a bucket (p, g, m, v: param, grad, exp_avg, exp_avg_sq at
+ * plane[b * shard_stride + e]), when skip is false:
+ *   g1  = g * c                              (also for c == 1.0f, where it is exact)
+ *   p1  = p * d
+ *   m'  = m * beta1 + g1 * o1
+ *   v'  = v * beta2 + (g1 * g1) * o2
+ *   den = sqrtf(v') / bias_corr2_sqrt + eps
+ *   p'  = p1 - ss * (m' / den)
+ * — torch.optim.AdamW (amsgrad = False) with m * beta1 + g * o1 written out in place of lerp.
+ * STORED: p', m' and v' to their planes; block b of EVERY rank row, rank b's included, receives
+ * bf16_rne(p') by all_gather_shards_f32's rounding rules.  skip: param, exp_avg and exp_avg_sq keep
+ * their bits (they are not written) and the rows receive bf16_rne(p).  With ALLRED_ADAMW_ZERO_GRAD
+ * every gradient element of the list is set to +0.0f, skipped step or not; without it grad is only
+ * read.  hyper and norm_sq are only read.  info, when given, receives {N, c, skip ? 1.0f : 0.0f,
+ * +0.0f}, written once, by the call's first launch.  Everything else keeps its bits: every byte
+ * outside the P blocks of blk floats of each plane, the gaps of a wide stride, the stride skew of
+ * the rows, memory past a row.
+ * CHECKS, all before any HIP call (a refused call writes nothing): the plan, count, buckets, rank-row
+ * rules and the 2^31 - 1 tile cap are those of the fp32 calls; a list with a bucket that is not whole
+ * tiles is ALLRED_ERR_UNSUPPORTED for the whole list.  ALLRED_ERR_ARG: a NULL plane pointer, a plane
+ * not 16-byte aligned, shard_stride < blk, shard_stride % 4 != 0, address arithmetic that would
+ * overflow, an unknown flag bit, hyper NULL or not 16-byte aligned, norm_sq not 4-byte aligned, info
+ * not 16-byte aligned.  count == 0: ALLRED_OK after the pointer checks, nothing is launched and info
+ * is NOT written.
+ * DISJOINTNESS (csrc/adamw_ranges.hpp; byte-exact and block-exact, else ALLRED_ERR_ARG): every
+ * bucket's rank-row interval, the 4 P count plane blocks of blk floats, [hyper, + 32),
+ * [norm_sq, + 4 P) and [info, + 16) are pairwise disjoint — param == grad, one plane named twice and
+ * info on a row are refused alike; hyper, norm_sq and info may lie in the gap of a wide stride.
+ * Four rank-major FLAT buffers, one per plane — F floats per rank, bucket i at column off_i,
+ * shard_stride = F — are accepted.
+ * LAUNCHES: a per-bucket entry is four pointers and a stride, so ONE launch covers
+ * ALLRED_ADAMW_GROUP_MAX = 32 buckets (the kernel arguments stay below 4 KiB):
+ * allred_plan_adamw_shards_f32_launches returns ceil(count / 32), or a negative status for
+ * arguments the call would refuse.  pipe_grid caps the grid like every persistent pass; no new
+ * tune keys. */
+#define ALLRED_ADAMW_GROUP_MAX 32      /* buckets one launch of this call covers */
+#define ALLRED_ADAMW_ZERO_GRAD 1       /* flags bit 0: store +0.0f over every gradient element read */
+typedef struct {                       /* 64 bytes */
+    uint16_t* ranks;                   /* as allred_shard_bucket_f32: bf16 rank rows, WRITTEN */
+    uint64_t  rank_stride;
+    uint64_t  elems_per_rank;
+    float*    param;                   /* fp32 master parameters, block b at param + b * shard_stride */
+    float*    grad;                    /* fp32 gradient shard: what reduce_scatter_shards_f32 filled */
+    float*    exp_avg;
+    float*    exp_avg_sq;
+    uint64_t  shard_stride;            /* floats; ONE stride for the four planes; >= blk, % 4 == 0 */
+} allred_adamw_bucket_f32;
+typedef struct {                       /* 32 bytes, lives in DEVICE memory, 16-byte aligned */
+    float lr, beta1, beta2, eps, weight_decay;
+    float bias_corr1;                  /* 1 - beta1^t          */
+    float bias_corr2_sqrt;             /* sqrt(1 - beta2^t)    */
+    float max_norm;                    /* +Inf: no clipping    */
+} allred_adamw_hyper;
+int allred_plan_adamw_all_gather_shards_f32(allred_plan* plan, const allred_adamw_bucket_f32* buckets, int count,
+                                            const allred_adamw_hyper* hyper /* device */,
+                                            const float* norm_sq /* [total], device, or NULL */,
+                                            float* info /* [4], device, or NULL */, int flags, void* stream);
+int allred_plan_adamw_shards_f32_launches(const allred_plan* plan, const allred_adamw_bucket_f32* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -33,6 +33,7 @@ __all__ = [
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
+    "adamw_hyper",
 ]
 
 
@@ -186,6 +187,17 @@ def validate_result_vector(result, src0, src1, num_els: int, error: float, total
     bad = lib.allred_validate_result_vector(arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
                                             num_els, error, total_nodes, int(verbose), C.byref(m))
     return int(bad), float(m.value)
+
+
+def adamw_hyper(lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, step: int = 1,
+                max_norm: float = float("inf")) -> np.ndarray:
+    """allred_adamw_hyper for optimizer step `step` (1-based) as eight float32: lr, beta1, beta2, eps,
+    weight_decay, 1 - beta1^step, sqrt(1 - beta2^step), max_norm.  The bias corrections are computed in
+    float64 and rounded once.  Copy the 32 bytes to device memory (16-byte aligned) before the call."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    bc1 = 1.0 - b1 ** int(step)
+    bc2_sqrt = float(np.sqrt(np.float64(1.0 - b2 ** int(step))))
+    return np.array([lr, b1, b2, eps, weight_decay, bc1, bc2_sqrt, max_norm], dtype=np.float32)
 
 
 # ---------------------------------------------------------------- device
@@ -372,6 +384,39 @@ class Plan:
         256-element tile of a rank row; 0 for a list the call would refuse."""
         arr, count = self._shard_buckets_f32(buckets)
         return int(lib.allred_plan_shards_f32_norm_workspace_bytes(self._h, arr, count))
+
+    @staticmethod
+    def _adamw_buckets_f32(buckets):
+        """a sequence of (ranks_ptr, stride, elems_per_rank, param_ptr, grad_ptr, exp_avg_ptr, exp_avg_sq_ptr,
+        shard_stride) — bf16 rank rows, four fp32 planes at one stride in floats — as an
+        allred_adamw_bucket_f32 array (None when empty)"""
+        items = [(int(p), int(s), int(n)) + tuple(int(x) if x else None for x in planes) + (int(shard_stride),)
+                 for p, s, n, *planes, shard_stride in buckets]
+        return ((_lib.AdamwBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def adamw_all_gather_shards_f32(self, buckets, hyper_ptr, norm_sq_ptr=None, info_ptr=None, zero_grad: bool = False,
+                                    stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_f32: the clipped AdamW step of allred.h on the fp32 planes
+        of every bucket, and block b of the new parameters rounded once to bf16 into block b of every
+        rank row — one launch per ALLRED_ADAMW_GROUP_MAX buckets.  hyper_ptr: the 32 bytes of
+        adamw_hyper(..) in device memory, 16-byte aligned; norm_sq_ptr: what
+        reduce_scatter_shards_f32_norm left (None: no clipping, no skip); info_ptr: 4 floats that
+        receive {N, c, skipped, 0} (None: not wanted); zero_grad: +0.0f over every gradient read."""
+        arr, count = self._adamw_buckets_f32(buckets)
+        flags = _lib.ADAMW_ZERO_GRAD if zero_grad else 0
+        check(lib.allred_plan_adamw_all_gather_shards_f32(self._h, arr, count, int(hyper_ptr) or None,
+                                                          int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None, flags,
+                                                          _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_f32")
+
+    def adamw_shards_f32_launches(self, buckets) -> int:
+        """Kernel launches adamw_all_gather_shards_f32 would enqueue for the list: one per
+        ALLRED_ADAMW_GROUP_MAX buckets."""
+        arr, count = self._adamw_buckets_f32(buckets)
+        st = lib.allred_plan_adamw_shards_f32_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_adamw_shards_f32_launches")
+        return st
 
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""

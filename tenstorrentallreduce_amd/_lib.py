@@ -152,6 +152,16 @@ class ShardBucketF32(C.Structure):   # allred_shard_bucket_f32: the shard is req
 SHARD_ACCUMULATE = 1   # ALLRED_SHARD_ACCUMULATE: allred_plan_reduce_scatter_shards_f32's flags bit 0
 
 
+class AdamwBucketF32(C.Structure):   # allred_adamw_bucket_f32: bf16 rank rows and four fp32 planes at ONE stride (floats)
+    _fields_ = [("ranks", C.c_void_p), ("rank_stride", C.c_uint64), ("elems_per_rank", C.c_uint64),
+                ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("shard_stride", C.c_uint64)]
+
+
+ADAMW_GROUP_MAX = 32   # ALLRED_ADAMW_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_f32 covers
+ADAMW_ZERO_GRAD = 1    # ALLRED_ADAMW_ZERO_GRAD: its flags bit 0
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -207,6 +217,8 @@ SIGNATURES = [
     ("allred_plan_shards_f32_norm_workspace_bytes", C.c_size_t, [_P, C.POINTER(ShardBucketF32), C.c_int]),
     ("allred_plan_reduce_scatter_shards_f32_norm", C.c_int,
      [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_float, C.c_int, _P, _P, _P]),
+    ("allred_plan_adamw_all_gather_shards_f32", C.c_int, [_P, C.POINTER(AdamwBucketF32), C.c_int, _P, _P, _P, C.c_int, _P]),
+    ("allred_plan_adamw_shards_f32_launches", C.c_int, [_P, C.POINTER(AdamwBucketF32), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

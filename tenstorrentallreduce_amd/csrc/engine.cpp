@@ -32,6 +32,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "adamw_ranges.hpp"
 #include "shard_f32_norm_ranges.hpp"
 #include "shard_f32_ranges.hpp"
 #include "shard_ranges.hpp"
@@ -987,6 +988,40 @@ int shards_f32_norm_check(const allred_plan* p, const allred_shard_bucket_f32* b
                : ALLRED_ERR_ARG;
 }
 
+// The checks of allred_plan_adamw_all_gather_shards_f32, all before any HIP call: the flags and
+// hyper, norm_sq and info — there where required, aligned —; the plan and the count as
+// shards_f32_check has them; every bucket's rank rows (group_check, the tile cap included); then
+// adamw_ranges.hpp's rules for the list: the four planes, the disjointness of rows, plane blocks and
+// the three small intervals (which also refuses address arithmetic that would overflow), and the one
+// kernel form's shape — a list with a bucket that is not whole tiles is ALLRED_ERR_UNSUPPORTED.
+// dry (the launch count's query): there is no hyper to check.
+int adamw_check(const allred_plan* p, const allred_adamw_bucket_f32* buckets, int count, const allred_adamw_hyper* hyper,
+                const float* norm_sq, const float* info, int flags, bool dry = false) {
+    if (!adamw_pointers_ok(hyper, norm_sq, info, flags, dry)) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    const uint64_t total = (uint64_t)p->total;
+    std::vector<AdamwRange> ranges((size_t)(count > 0 ? count : 0));
+    if (count > 0) {
+        if (!buckets) return ALLRED_ERR_ARG;
+        std::vector<allred_bucket> plain((size_t)count);
+        for (int i = 0; i < count; ++i)
+            plain[(size_t)i] = allred_bucket{buckets[i].ranks, buckets[i].rank_stride, buckets[i].elems_per_rank};
+        const int st = group_check(p, plain.data(), count);
+        if (st != ALLRED_OK) return st;
+        for (int i = 0; i < count; ++i) {
+            const allred_adamw_bucket_f32& b = buckets[i];
+            ranges[(size_t)i] = AdamwRange{b.ranks, b.rank_stride, b.elems_per_rank, {b.param, b.grad, b.exp_avg, b.exp_avg_sq},
+                                           b.shard_stride};
+        }
+    }
+    switch (adamw_list_verdict(ranges.data(), count, total, hyper, norm_sq, info)) {
+        case kAdamwOk: return ALLRED_OK;
+        case kAdamwUnsupported: return ALLRED_ERR_UNSUPPORTED;
+        default: return ALLRED_ERR_ARG;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1033,6 +1068,23 @@ int allred_plan_reduce_scatter_shards_f32_norm(allred_plan* p, const allred_shar
     if (!guard.ok) return ALLRED_ERR_HIP;
     return launch_shard_group_f32(buckets, count, p->total, p->d_order, ALLRED_OP_REDUCE_SCATTER, scale,
                                   (flags & ALLRED_SHARD_ACCUMULATE) != 0, /*dry=*/false, stream, norm_sq, norm_ws);
+}
+
+int allred_plan_adamw_all_gather_shards_f32(allred_plan* p, const allred_adamw_bucket_f32* buckets, int count,
+                                            const allred_adamw_hyper* hyper, const float* norm_sq, float* info, int flags,
+                                            void* stream) {
+    const int st = adamw_check(p, buckets, count, hyper, norm_sq, info, flags);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_f32(buckets, count, p->total, hyper, norm_sq, info, (flags & ALLRED_ADAMW_ZERO_GRAD) != 0,
+                                  /*dry=*/false, stream);
+}
+
+int allred_plan_adamw_shards_f32_launches(const allred_plan* p, const allred_adamw_bucket_f32* buckets, int count) {
+    const int st = adamw_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_adamw_group_f32(buckets, count, p->total, nullptr, nullptr, nullptr, false, /*dry=*/true, nullptr);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -114,6 +114,11 @@ int launch_shard_group(const allred_shard_bucket* buckets, int count, int total,
 int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, int total, const uint8_t* order, int op,
                            float scale, bool accumulate, bool dry, void* stream, float* norm_sq = nullptr,
                            void* norm_ws = nullptr);
+// a list of (checked) whole-tile buckets with their four fp32 planes (adamw_kernels.hip): the clipped AdamW
+// step of allred.h on the planes and p' rounded once to bf16 into every rank row — k_adamw_ag_group_f32 —,
+// ALLRED_ADAMW_GROUP_MAX buckets per launch; info goes to the first launch alone.  dry: as above.
+int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, int count, int total, const allred_adamw_hyper* hyper,
+                           const float* norm_sq, float* info, bool zero_grad, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
