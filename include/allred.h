@@ -208,7 +208,10 @@ int allred_broadcast(uint16_t* ranks, uint64_t rank_stride, size_t n, int total_
  * mismatch out of its maximum (a quirk of the reference's loop, allred_helper.cpp:49-75);
  * this one does not, so the two maxima may differ by that one element.
  * Enqueues on `stream` (counters zeroed by a stream-ordered memset, the launch, the copy of the
- * `rows` records to out[], host memory) and returns once the records are on the host.
+ * `rows` records to out[], host memory) and returns once the records are on the host: it
+ * synchronizes `stream` by design and must not be called while the stream is being captured
+ * into a graph.  Every other call of this header that takes a plan and a stream only enqueues
+ * kernel launches and can be captured.
  * ALLRED_ERR_ARG before any HIP call: a null pointer, n == 0 or n % 8 != 0, rows < 1 or
  * rows > ALLRED_MAX_NODES, rank_stride < n or % 8 != 0, a pointer not 16-byte aligned.
  * Nothing past element n of a row is read (the stride skew holds no data). */

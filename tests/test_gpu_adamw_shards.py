@@ -19,6 +19,7 @@ import adamw_cases
 import adamw_ref
 import f32_norm
 import f32_tree
+import far_arena
 import tenstorrentallreduce_amd as t
 import test_gpu_shards_f32 as base
 from tenstorrentallreduce_amd import _lib
@@ -449,3 +450,50 @@ def test_hyper_norm_sq_and_info_in_the_gaps_of_a_wide_stride():
     planes.check(values, "the three in a gap")
     base.check_buckets(buckets, [b.after_all_gather(r) for b, r in zip(buckets, rows)], "rows", by_class=True)
     plan.close()
+
+
+# ------------------------------------------------------------------ rows and planes beyond 2^32 elements
+@pytest.fixture(scope="module")
+def far():
+    f = far_arena.F32Far(planes=4)   # an allocation failure is an error of the test, not a skip
+    yield f
+    f.close()
+
+
+def test_far_rows_and_four_far_planes_in_one_flat_buffer(far):
+    """8x8 Swing, buckets of 1 and 3 tiles per block, the rank rows of the larger at the far bf16 stride and the four
+    planes of both buckets at eight column offsets of ONE flat fp32 buffer of row stride
+    F = roundup4(ceil(2^32 / 63)) + 64 floats (tests/far_arena.py): 63 F is beyond 2^32 floats.  The
+    clipped step with zero_grad: p' g m' v' and every row bit for bit tests/adamw_ref.py's, every guard
+    intact, the whole arena sentinel again."""
+    algo, side, total = t.SWING, 8, 64
+    shapes = [(total, 256 * k) for k in far_arena.F32_TILES]
+    data = [adamw_cases.planes(80 + i, shape) for i, shape in enumerate(shapes)]
+    for i, (rows, d) in enumerate(zip(far.rows, data)):
+        rows.upload(base.inputs("soft", total, rows.set.width, 5))   # all of it is overwritten
+        for k in range(4):
+            far.planes[i][k].upload(d[k])
+    args = [far.bucket(i) + tuple(far.planes[i][k].ptr for k in range(4)) + (far.stride_f32,) for i in range(len(data))]
+    hyper, nsq = adamw_cases.hyper(), adamw_cases.norm_sq(total)
+    small = Small(hyper, nsq)
+    plan = base.any_plan(algo, side, total)
+    try:
+        with t.tuned(pipe_grid=5):
+            assert plan.adamw_shards_f32_launches(args) == 1
+            with t.launch_trace() as tr:
+                plan.adamw_all_gather_shards_f32(args, small.hyper, small.norm_sq, small.info, zero_grad=True, stream=stream())
+            torch.cuda.synchronize()
+        assert tr.kernels == [f"k_adamw_ag_group_f32<{total}, true>"]
+        values, rows16, info = expect(data, hyper, nsq, total, True)
+        assert info[1] < 1 and info[2] == 0   # clipping is active, the step is not skipped
+        for i in range(len(data)):
+            for k in range(4):
+                assert f32_tree.same_f32(far.planes[i][k].read().view(np.float32), values[i][k]), f"bucket {i} {NAMES[k]}"
+            n = far.rows[i].set.width
+            want = np.broadcast_to(np.ascontiguousarray(rows16[i]).reshape(-1), (total, n))
+            assert f32_tree.same_bf16(far.rows[i].read(), want), f"bucket {i}: rows = bf16_rne(p')"
+        small.check(info, "far rows, far planes")
+    finally:
+        plan.close()
+        far.wipe()
+    far.assert_sentinel()

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import f32_tree
+import far_arena
 import hard_inputs
 import route_cases
 import tenstorrentallreduce_amd as t
@@ -569,3 +570,54 @@ def test_a_non_finite_scale_is_the_callers_arithmetic():
     got = shards.blocks(0, shards.got()).view(np.uint32)
     assert (got == 0x7F800000).all()   # positive sums x +Inf
     plan.close()
+
+
+# ------------------------------------------------------------------ 6. rows and shards beyond 2^32 elements
+@pytest.fixture(scope="module")
+def far():
+    f = far_arena.F32Far(planes=1)   # an allocation failure is an error of the test, not a skip
+    yield f
+    f.close()
+
+
+def far_args(far):
+    """bucket i: its far rank rows, and its blocks of the flat fp32 buffer, F floats apart"""
+    return [far.bucket(i) + (far.planes[i][0].ptr, far.stride_f32) for i in range(len(far.rows))]
+
+
+def test_far_rows_and_a_far_flat_shard_buffer(far):
+    """8x8 Swing, buckets of 1 and 3 tiles per block (tests/far_arena.py): the rank rows of the larger at the far
+    bf16 stride (a list takes no two buckets whose row footprints meet), the shards blocks of ONE flat fp32 buffer of row stride F = roundup4(ceil(2^32 / 63)) + 64
+    floats — 63 F is beyond 2^32 floats, middle blocks beyond 2^30 and 2^31.  The reduce-scatter, then
+    the all-gather of what it stored: every payload row with 4 KiB of guard on both sides bit for bit,
+    then the whole arena sentinel again.  `shard + b * shard_stride` or `ranks + r * stride` in 32 bits
+    fails the compare (tests/test_far_layout.py)."""
+    algo, side, total = t.SWING, 8, 64
+    scale = 1.0 / total
+    datas = [sums("cancel", algo, side, total, 256 * total * k, 300 + i) for i, k in enumerate(far_arena.F32_TILES)]
+    for rows, (data, _) in zip(far.rows, datas):
+        rows.upload(data)
+    args = far_args(far)
+    plan = any_plan(algo, side, total)
+    try:
+        with t.tuned(pipe_grid=5):
+            with t.launch_trace() as tr:
+                plan.reduce_scatter_shards_f32(args, scale, stream=stream())
+            torch.cuda.synchronize()
+            assert tr.kernels == [f"k_tree_group_f32<{total}, false>"]
+            stored = [f32_tree.scaled(s, scale) for _, s in datas]
+            for i, (data, _) in enumerate(datas):
+                assert f32_tree.same_f32(far.planes[i][0].read().view(np.float32), stored[i]), f"bucket {i}: block b = fp32 tree b x scale"
+                assert np.array_equal(far.rows[i].read(), data), f"bucket {i}: the rank rows are only read"
+            with t.launch_trace() as tr:
+                plan.all_gather_shards_f32(args, stream())
+            torch.cuda.synchronize()
+            assert tr.kernels == [f"k_ag_group_f32<{total}>"]
+            for i, (data, _) in enumerate(datas):
+                row = f32_tree.bf16_rne(stored[i]).reshape(-1)
+                assert f32_tree.same_bf16(far.rows[i].read(), np.broadcast_to(row, data.shape)), f"bucket {i}: block b of every row"
+                assert f32_tree.same_f32(far.planes[i][0].read().view(np.float32), stored[i]), f"bucket {i}: an all-gather wrote its shard"
+    finally:
+        plan.close()
+        far.wipe()
+    far.assert_sentinel()

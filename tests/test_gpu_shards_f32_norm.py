@@ -20,6 +20,7 @@ import pytest
 
 import f32_norm
 import f32_norm_cases as cases
+import far_arena
 import f32_tree
 import tenstorrentallreduce_amd as t
 import test_gpu_shards_f32 as base
@@ -401,3 +402,36 @@ def test_refusals_write_nothing():
     for g, e in zip(gap_sq, want):
         assert f32_tree.same_f32(g.view(np.float32), e.view(np.float32)), "norm_sq in the gap of a wide stride"
     plan.close()
+
+
+# ------------------------------------------------------------------ rows and shards beyond 2^32 elements
+far = base.far   # the module-scoped arena fixture of tests/test_gpu_shards_f32.py: one arena per module
+
+
+def test_far_rows_and_a_far_flat_shard_buffer(far):
+    """The far layout of tests/test_gpu_shards_f32.py (8x8 Swing, 1 and 3 tiles per block, 63 F beyond
+    2^32 floats): the shards bit for bit tests/f32_tree.py's, norm_sq tests/f32_norm.py's, the rank
+    rows only read, every guard intact and the whole arena sentinel again."""
+    algo, side, total = t.SWING, 8, 64
+    scale = 1.0 / total
+    datas = cases.bucket_list(algo, side, total, far_arena.F32_TILES, seed=3)
+    for rows, (data, _) in zip(far.rows, datas):
+        rows.upload(data)
+    args = base.far_args(far)
+    plan = base.any_plan(algo, side, total)
+    norm = Norm(plan, args, total)
+    try:
+        with t.tuned(pipe_grid=5):
+            with t.launch_trace() as tr:
+                call(plan, None, norm, scale, args=args)
+            torch.cuda.synchronize()
+            assert tr.kernels == [f"k_tree_group_f32_norm<{total}, false>"]
+            values = cases.stored(datas, scale)
+            for i, (data, _) in enumerate(datas):
+                assert f32_tree.same_f32(far.planes[i][0].read().view(np.float32), values[i]), f"bucket {i}: the shard"
+                assert np.array_equal(far.rows[i].read(), data), f"bucket {i}: the rank rows are only read"
+            norm.check(f32_norm.expect_norm_sq(values), "far rows, far shards")
+    finally:
+        plan.close()
+        far.wipe()
+    far.assert_sentinel()
