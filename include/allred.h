@@ -47,6 +47,8 @@ extern "C" {
  * Still ABI 7: allred_adamw_bucket_f32, allred_adamw_hyper, ALLRED_ADAMW_GROUP_MAX, ALLRED_ADAMW_ZERO_GRAD and
  * allred_plan_adamw_all_gather_shards_f32 / allred_plan_adamw_shards_f32_launches are additions — the
  * clipped AdamW step on the fp32 shards inside the grouped all-gather's launch.
+ * Still ABI 7: ALLRED_ADAMW_PARAM_GROUPS_MAX and allred_plan_adamw_all_gather_shards_f32_groups are additions —
+ * the same step with a hyperparameter set per parameter group, chosen per bucket, in the same launches.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -579,7 +581,53 @@ int allred_plan_adamw_all_gather_shards_f32(allred_plan* plan, const allred_adam
                                             const allred_adamw_hyper* hyper /* device */,
                                             const float* norm_sq /* [total], device, or NULL */,
                                             float* info /* [4], device, or NULL */, int flags, void* stream);
+/* Also the launch count of allred_plan_adamw_all_gather_shards_f32_groups below: its launches are the
+ * same ceil(count / 32), in list order, whatever the groups are. */
 int allred_plan_adamw_shards_f32_launches(const allred_plan* plan, const allred_adamw_bucket_f32* buckets, int count);
+
+/* ADAMW PARAMETER GROUPS, STILL ONE LAUNCH PER 32 BUCKETS: allred_plan_adamw_all_gather_shards_f32
+ * with a hyperparameter set per PARAMETER GROUP (torch.optim.AdamW's param_groups: biases and norm
+ * weights with weight_decay = 0, layers with an lr of their own) instead of one set per call.
+ * hyper is a DEVICE array of ngroups sets of 32 bytes (1 <= ngroups <= ALLRED_ADAMW_PARAM_GROUPS_MAX,
+ * 16-byte aligned, only read, rewritten by the caller between graph replays like the one set);
+ * group_of is a HOST array of count bytes, read during the call only: bucket i uses
+ * hyper[group_of[i]].  group_of == NULL: every bucket is in group 0.  The kernel traces as
+ * k_adamw_ag_groups_f32<P, false|true> (csrc/adamw_groups_kernels.hip), ALSO for ngroups == 1: the
+ * call has one kernel form, no routing rule and no tune key.  No reference counterpart.
+ * SEMANTICS: those of allred_plan_adamw_all_gather_shards_f32 above, with two changes.
+ *   CALL-WIDE: N, skip and c are ONE value for the whole call — gradient clipping is by the global
+ *   norm over all groups, as torch.nn.utils.clip_grad_norm_ over all parameters does —, by the
+ *   formulas above, with max_norm = hyper[0].max_norm.  The max_norm field of hyper[1 .. ngroups - 1]
+ *   is NEVER USED.  info, when given, receives {N, c, skip ? 1.0f : 0.0f, +0.0f}, written once, by
+ *   the call's first launch.
+ *   PER GROUP: d, o1, o2, ss, beta1, beta2, eps and bias_corr2_sqrt are group g's, from hyper[g] by
+ *   the same single fp32 operations as above (d = 1.0f - lr * weight_decay; o1 = 1.0f - beta1;
+ *   o2 = 1.0f - beta2; ss = lr / bias_corr1); every element of bucket i takes group group_of[i]'s.
+ * Everything else is the call's above, word for word: the per-element operations and their order (one
+ * IEEE fp32 operation each, never an fma, division and square root correctly rounded, denormals
+ * kept), what is STORED, the skipped step (param, exp_avg and exp_avg_sq keep their bits, the rows
+ * receive bf16_rne(p)), ALLRED_ADAMW_ZERO_GRAD, and what keeps its bits.
+ * GUARANTEE (tests/test_gpu_adamw_groups.py): for every bucket i the four planes and the rank rows
+ * are bit for bit what allred_plan_adamw_all_gather_shards_f32 gives that bucket with the set
+ * hyper[group_of[i]] whose max_norm is replaced by hyper[0].max_norm, and the same norm_sq.
+ * CHECKS, all before any HIP call (a refused call writes nothing): every check of the call above,
+ * unchanged, plus ALLRED_ERR_ARG for ngroups < 1 or > ALLRED_ADAMW_PARAM_GROUPS_MAX and for a
+ * group_of[i] >= ngroups.  count == 0: ALLRED_OK after the pointer and ngroups checks, nothing is
+ * launched and info is NOT written.
+ * DISJOINTNESS: the rule above with the WHOLE array [hyper, + 32 ngroups) in place of [hyper, + 32):
+ * it shares no byte with a rank-row interval, a plane block, norm_sq or info — info inside
+ * hyper[ngroups - 1] is refused —, and may lie in the gap of a wide shard_stride.
+ * LAUNCHES: ALLRED_ADAMW_GROUP_MAX = 32 buckets each, in list order, whatever the groups are — the
+ * buckets of a group need not be adjacent; allred_plan_adamw_shards_f32_launches answers for this
+ * call too.  The per-launch group table (one byte per bucket) travels by value: 3408 bytes of kernel
+ * arguments. */
+#define ALLRED_ADAMW_PARAM_GROUPS_MAX 8   /* hyperparameter sets one call takes */
+int allred_plan_adamw_all_gather_shards_f32_groups(
+    allred_plan* plan, const allred_adamw_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, void* stream);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

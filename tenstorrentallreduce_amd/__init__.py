@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ACC_BF16, ACC_FP32, BO, EXEC_FUSED, EXEC_STEPS, LO, MEM, MULTI_FLAT, MULTI_HIER,  # noqa: F401
                    MULTI_LOCAL, OP_ALL_GATHER, OP_REDUCE_SCATTER, RECDUB, RECDUB_1D, SWING, SWING_1D, TRANSPORT_HOST,
-                   TRANSPORT_PEER, TRANSPORT_RCCL, AllredError, Args, DistDesc, MultiOpts, MultiPlan, PlanDesc, Report, Schedule, Seg, check, lib)
+                   TRANSPORT_PEER, TRANSPORT_RCCL, ADAMW_PARAM_GROUPS_MAX, AllredError, Args, DistDesc, MultiOpts, MultiPlan, PlanDesc, Report, Schedule, Seg, check, lib)
 
 __all__ = [
     "BO", "LO", "MEM", "SWING", "RECDUB", "SWING_1D", "RECDUB_1D", "get_comm_partner_swing_1D",
@@ -33,7 +33,7 @@ __all__ = [
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
-    "adamw_hyper",
+    "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX",
 ]
 
 
@@ -198,6 +198,18 @@ def adamw_hyper(lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: 
     bc1 = 1.0 - b1 ** int(step)
     bc2_sqrt = float(np.sqrt(np.float64(1.0 - b2 ** int(step))))
     return np.array([lr, b1, b2, eps, weight_decay, bc1, bc2_sqrt, max_norm], dtype=np.float32)
+
+
+def adamw_hyper_groups(groups, step: int = 1, max_norm: float = float("inf")) -> np.ndarray:
+    """The hyper array of Plan.adamw_all_gather_shards_f32_groups for a list of parameter groups — dicts
+    with torch.optim.AdamW's keys lr, betas, eps, weight_decay (a missing key: adamw_hyper's default) —
+    as (G, 8) float32, row g made by adamw_hyper.  max_norm is the CALL's (clipping is by the global
+    norm over all groups); it is written into every row, and row 0's is the one the kernel reads."""
+    groups = list(groups)
+    if not 1 <= len(groups) <= ADAMW_PARAM_GROUPS_MAX:
+        raise ValueError(f"1 .. {ADAMW_PARAM_GROUPS_MAX} parameter groups, not {len(groups)}")
+    keys = ("lr", "betas", "eps", "weight_decay")
+    return np.stack([adamw_hyper(**{k: g[k] for k in keys if k in g}, step=step, max_norm=max_norm) for g in groups])
 
 
 # ---------------------------------------------------------------- device
@@ -409,9 +421,30 @@ class Plan:
                                                           _stream_ptr(stream)),
               "plan_adamw_all_gather_shards_f32")
 
+    def adamw_all_gather_shards_f32_groups(self, buckets, group_of, hyper_ptr, ngroups: int, norm_sq_ptr=None, info_ptr=None,
+                                           zero_grad: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_f32_groups: adamw_all_gather_shards_f32 with a hyperparameter
+        set per parameter group, still one launch per ALLRED_ADAMW_GROUP_MAX buckets.  group_of: one
+        group index per bucket (None: every bucket in group 0); hyper_ptr: the ngroups x 32 bytes of
+        adamw_hyper_groups(..) in device memory, 16-byte aligned.  N, the skip and the clip
+        coefficient are the call's (max_norm: row 0's); everything else is the group's."""
+        arr, count = self._adamw_buckets_f32(buckets)
+        groups = None
+        if group_of is not None:
+            if len(group_of) != count:
+                raise ValueError(f"{len(group_of)} group indices for {count} buckets")
+            if any(not 0 <= int(g) <= 255 for g in group_of):
+                raise ValueError("a group index is one byte")
+            groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
+        flags = _lib.ADAMW_ZERO_GRAD if zero_grad else 0
+        check(lib.allred_plan_adamw_all_gather_shards_f32_groups(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups),
+                                                                 int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None,
+                                                                 flags, _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_f32_groups")
+
     def adamw_shards_f32_launches(self, buckets) -> int:
-        """Kernel launches adamw_all_gather_shards_f32 would enqueue for the list: one per
-        ALLRED_ADAMW_GROUP_MAX buckets."""
+        """Kernel launches adamw_all_gather_shards_f32 — and adamw_all_gather_shards_f32_groups, whatever
+        the groups — would enqueue for the list: one per ALLRED_ADAMW_GROUP_MAX buckets."""
         arr, count = self._adamw_buckets_f32(buckets)
         st = lib.allred_plan_adamw_shards_f32_launches(self._h, arr, count)
         if st < 0:

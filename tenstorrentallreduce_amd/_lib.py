@@ -160,6 +160,7 @@ class AdamwBucketF32(C.Structure):   # allred_adamw_bucket_f32: bf16 rank rows a
 
 ADAMW_GROUP_MAX = 32   # ALLRED_ADAMW_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_f32 covers
 ADAMW_ZERO_GRAD = 1    # ALLRED_ADAMW_ZERO_GRAD: its flags bit 0
+ADAMW_PARAM_GROUPS_MAX = 8   # ALLRED_ADAMW_PARAM_GROUPS_MAX: hyper sets one allred_plan_adamw_all_gather_shards_f32_groups takes
 
 
 class Seg(C.Structure):
@@ -219,6 +220,8 @@ SIGNATURES = [
      [_P, C.POINTER(ShardBucketF32), C.c_int, C.c_float, C.c_int, _P, _P, _P]),
     ("allred_plan_adamw_all_gather_shards_f32", C.c_int, [_P, C.POINTER(AdamwBucketF32), C.c_int, _P, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_f32_launches", C.c_int, [_P, C.POINTER(AdamwBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_f32_groups", C.c_int,
+     [_P, C.POINTER(AdamwBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -7,6 +7,8 @@
 //   the 4 P count plane blocks            [plane + 4 b shard_stride, + 4 blk), blk = n / total —
 //                                         param, grad, exp_avg and exp_avg_sq of every bucket;
 //   [hyper, + 32)   [norm_sq, + 4 total) (when given)   [info, + 16) (when given).
+// allred_plan_adamw_all_gather_shards_f32_groups reads an ARRAY of hyper sets: its interval is
+// [hyper, + 32 ngroups), passed as hyper_bytes (defaulted to the one set's 32), under the same rule.
 // A bucket is four ShardF32Ranges — one with the rows and the parameter plane, three with
 // ranks = nullptr and stride 0 (no row interval) and one of the other planes — and
 // shard_f32_lists_disjoint answers for the 4 count of them unchanged: its verdict does not depend
@@ -27,6 +29,7 @@
 namespace tsa {
 
 constexpr uint64_t kAdamwHyperBytes = 32, kAdamwInfoBytes = 16;
+constexpr int kAdamwParamGroupsMax = 8;   // ALLRED_ADAMW_PARAM_GROUPS_MAX (allred.h)
 
 struct AdamwRange {
     const void* ranks;       // rank 0's row of bf16
@@ -48,9 +51,9 @@ inline void adamw_as_f32_ranges(const AdamwRange* list, int count, std::vector<S
 
 // true: every interval above lies in the address space and no two share a byte.  total >= 1; every
 // n a multiple of total; every plane non-null (the caller's checks).  hyper / norm_sq / info:
-// nullptr = not given.
+// nullptr = not given.  hyper_bytes: the length of hyper's interval, 32 per hyper set.
 inline bool adamw_lists_disjoint(const AdamwRange* list, int count, uint64_t total, const void* hyper, const void* norm_sq,
-                                 const void* info) {
+                                 const void* info, uint64_t hyper_bytes = kAdamwHyperBytes) {
     if (count > 0 && (!list || total == 0)) return false;
     std::vector<ShardF32Range> ranges;
     adamw_as_f32_ranges(list, count, &ranges);
@@ -58,7 +61,7 @@ inline bool adamw_lists_disjoint(const AdamwRange* list, int count, uint64_t tot
     uint64_t bytes;
     if (__builtin_mul_overflow(total, (uint64_t)4, &bytes)) return false;
     const uint64_t lo[3] = {(uint64_t)(uintptr_t)hyper, (uint64_t)(uintptr_t)norm_sq, (uint64_t)(uintptr_t)info};
-    const uint64_t len[3] = {hyper ? kAdamwHyperBytes : 0, norm_sq ? bytes : 0, info ? kAdamwInfoBytes : 0};
+    const uint64_t len[3] = {hyper ? hyper_bytes : 0, norm_sq ? bytes : 0, info ? kAdamwInfoBytes : 0};
     uint64_t hi[3];
     for (int k = 0; k < 3; ++k)
         if (__builtin_add_overflow(lo[k], len[k], &hi[k]) || hi[k] > (uint64_t)UINTPTR_MAX) return false;
@@ -89,7 +92,7 @@ inline bool adamw_pointers_ok(const void* hyper, const void* norm_sq, const void
 // shard_stride < blk or % 4 != 0, address arithmetic that would overflow, two intervals sharing a
 // byte; then kAdamwUnsupported for the whole list: a bucket that is not whole tiles.
 inline AdamwVerdict adamw_list_verdict(const AdamwRange* list, int count, uint64_t total, const void* hyper,
-                                       const void* norm_sq, const void* info) {
+                                       const void* norm_sq, const void* info, uint64_t hyper_bytes = kAdamwHyperBytes) {
     if (count > 0 && (!list || total == 0)) return kAdamwArg;
     for (int i = 0; i < count; ++i) {
         const AdamwRange& a = list[i];
@@ -97,10 +100,21 @@ inline AdamwVerdict adamw_list_verdict(const AdamwRange* list, int count, uint64
             if (!q || (uintptr_t)q % 16) return kAdamwArg;
         if (a.shard_stride < a.n / total || a.shard_stride % 4) return kAdamwArg;
     }
-    if (!adamw_lists_disjoint(list, count, total, hyper, norm_sq, info)) return kAdamwArg;
+    if (!adamw_lists_disjoint(list, count, total, hyper, norm_sq, info, hyper_bytes)) return kAdamwArg;
     for (int i = 0; i < count; ++i)
         if (total < 8 || list[i].n % (256 * total)) return kAdamwUnsupported;
     return kAdamwOk;
+}
+
+// The two group rules of allred_plan_adamw_all_gather_shards_f32_groups: 1 <= ngroups <=
+// kAdamwParamGroupsMax, and every group_of[i], i < count, below ngroups.  group_of == nullptr: every
+// bucket is in group 0, which exists.  count <= 0: only ngroups is looked at.
+inline bool adamw_groups_ok(const uint8_t* group_of, int count, int ngroups) {
+    if (ngroups < 1 || ngroups > kAdamwParamGroupsMax) return false;
+    if (!group_of) return true;
+    for (int i = 0; i < count; ++i)
+        if (group_of[i] >= ngroups) return false;
+    return true;
 }
 
 }  // namespace tsa

@@ -994,9 +994,12 @@ int shards_f32_norm_check(const allred_plan* p, const allred_shard_bucket_f32* b
 // adamw_ranges.hpp's rules for the list: the four planes, the disjointness of rows, plane blocks and
 // the three small intervals (which also refuses address arithmetic that would overflow), and the one
 // kernel form's shape — a list with a bucket that is not whole tiles is ALLRED_ERR_UNSUPPORTED.
-// dry (the launch count's query): there is no hyper to check.
+// dry (the launch count's query): there is no hyper to check.  hyper_bytes: the length of hyper's
+// interval — 32, or 32 ngroups for allred_plan_adamw_all_gather_shards_f32_groups.
+static_assert(kAdamwParamGroupsMax == ALLRED_ADAMW_PARAM_GROUPS_MAX, "adamw_ranges.hpp's copy of allred.h's constant");
 int adamw_check(const allred_plan* p, const allred_adamw_bucket_f32* buckets, int count, const allred_adamw_hyper* hyper,
-                const float* norm_sq, const float* info, int flags, bool dry = false) {
+                const float* norm_sq, const float* info, int flags, bool dry = false,
+                uint64_t hyper_bytes = kAdamwHyperBytes) {
     if (!adamw_pointers_ok(hyper, norm_sq, info, flags, dry)) return ALLRED_ERR_ARG;
     if (!p || count < 0) return ALLRED_ERR_ARG;
     if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
@@ -1015,7 +1018,7 @@ int adamw_check(const allred_plan* p, const allred_adamw_bucket_f32* buckets, in
                                            b.shard_stride};
         }
     }
-    switch (adamw_list_verdict(ranges.data(), count, total, hyper, norm_sq, info)) {
+    switch (adamw_list_verdict(ranges.data(), count, total, hyper, norm_sq, info, hyper_bytes)) {
         case kAdamwOk: return ALLRED_OK;
         case kAdamwUnsupported: return ALLRED_ERR_UNSUPPORTED;
         default: return ALLRED_ERR_ARG;
@@ -1079,6 +1082,21 @@ int allred_plan_adamw_all_gather_shards_f32(allred_plan* p, const allred_adamw_b
     if (!guard.ok) return ALLRED_ERR_HIP;
     return launch_adamw_group_f32(buckets, count, p->total, hyper, norm_sq, info, (flags & ALLRED_ADAMW_ZERO_GRAD) != 0,
                                   /*dry=*/false, stream);
+}
+
+// The group rules first (adamw_ranges.hpp adamw_groups_ok: ngroups, every group index), then
+// adamw_check with the whole hyper array as hyper's interval; all of it before any HIP call.
+int allred_plan_adamw_all_gather_shards_f32_groups(allred_plan* p, const allred_adamw_bucket_f32* buckets,
+                                                   const uint8_t* group_of, int count, const allred_adamw_hyper* hyper,
+                                                   int ngroups, const float* norm_sq, float* info, int flags, void* stream) {
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_check(p, buckets, count, hyper, norm_sq, info, flags, /*dry=*/false,
+                               kAdamwHyperBytes * (uint64_t)ngroups);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_groups_f32(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                   (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, stream);
 }
 
 int allred_plan_adamw_shards_f32_launches(const allred_plan* p, const allred_adamw_bucket_f32* buckets, int count) {

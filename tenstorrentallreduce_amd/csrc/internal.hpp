@@ -119,6 +119,11 @@ int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, in
 // ALLRED_ADAMW_GROUP_MAX buckets per launch; info goes to the first launch alone.  dry: as above.
 int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, int count, int total, const allred_adamw_hyper* hyper,
                            const float* norm_sq, float* info, bool zero_grad, bool dry, void* stream);
+// the same list with a parameter group per bucket (adamw_groups_kernels.hip; group_of == nullptr: group 0) and
+// hyper an array of ngroups sets — k_adamw_ag_groups_f32 —, the same 32 buckets per launch in list order
+int launch_adamw_groups_f32(const allred_adamw_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                            const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                            void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
