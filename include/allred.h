@@ -49,6 +49,9 @@ extern "C" {
  * clipped AdamW step on the fp32 shards inside the grouped all-gather's launch.
  * Still ABI 7: ALLRED_ADAMW_PARAM_GROUPS_MAX and allred_plan_adamw_all_gather_shards_f32_groups are additions —
  * the same step with a hyperparameter set per parameter group, chosen per bucket, in the same launches.
+ * Still ABI 7: allred_mx_bucket_f32, ALLRED_MX_GROUP_MAX, ALLRED_MX_SCALE_RCEIL and
+ * allred_plan_all_gather_shards_mxfp8 / allred_plan_all_gather_shards_mxfp8_launches are additions — the grouped
+ * all-gather from fp32 shards into MXFP8 rows: e4m3 bytes and one E8M0 scale byte per 32 elements.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -628,6 +631,70 @@ int allred_plan_adamw_all_gather_shards_f32_groups(
     const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, void* stream);
+
+/* MXFP8 ALL-GATHER FROM THE FP32 SHARDS: allred_plan_all_gather_shards_f32 for a step that takes its
+ * weights as OCP MX operands (the block-scaled f8f6f4 MFMA of the MI355X): every rank row receives the
+ * shard's values as e4m3fn BYTES, and a parallel SCALE ROW receives one E8M0 byte per 32 elements.
+ * The value is rounded once, from the fp32 master, in the launch that gathers it: no bf16 intermediate
+ * and no quantisation pass over every rank's copy; 1.03125 bytes written per element instead of 2.
+ * Accepted plans and blk = elems_per_rank / total are those of the fp32 shard calls above; the plan
+ * supplies P only.  blk is a multiple of 256, so a 32-element MX block never straddles a shard block.
+ * The kernel traces as k_ag_group_mxfp8<P, false|true> (csrc/mx_kernels.hip; the bool:
+ * ALLRED_MX_SCALE_RCEIL).  No reference counterpart.
+ * SEMANTICS.  Every output bit is a function of the input bits.  Take each aligned group of 32
+ * consecutive floats x_0 .. x_31 of block b of a bucket (elements e .. e + 31 of the block, e % 32 == 0).
+ * Block b of EVERY rank row, rank b's included, receives the same 32 element bytes, at byte
+ * b * blk + e + i of the row; byte (b * blk + e) / 32 of EVERY scale row receives the same scale byte.
+ *   A = the largest bits(x_i) & 0x7fffffff, compared as integers.
+ *   A >= 0x7f800000 (a NaN or +-Inf in the block): scale byte 0xFF and all 32 element bytes 0x7F — an
+ *     MX block with a NaN scale is all NaN.  This is the found-inf signal on the consumer's side.
+ *   Otherwise:
+ *     E = (A >> 23) - 127                      (-127 for zero and for denormals)
+ *     X = E - 8                                (the floor rule of OCP MX v1.0), or, with
+ *         ALLRED_MX_SCALE_RCEIL, X = E - 8 + ((A & 0x7fffff) > 0x600000 ? 1 : 0): ceil(log2(amax / 448)),
+ *         under which no finite element saturates;
+ *     X is clamped below at -127 (the upper clamp cannot bind: X <= 120);   scale byte = X + 127.
+ *   y_i = x_i * 2^(-X): ONE fp32 multiply, denormals kept (2^(-X) is a normal fp32 for every reachable X).
+ *   element byte = y_i rounded to e4m3fn: IEEE round to nearest even, subnormals as multiples of 2^-9;
+ *     |y_i| > 448 gives +-448 (0x7E / 0xFE), never the NaN encoding; the sign is always kept: -0 and a
+ *     negative value that rounds to zero both give 0x80.
+ * The shard is only read.  Per row only elems_per_rank bytes of `rows` and elems_per_rank / 32 bytes of
+ * `scales` are written; every other byte keeps its bits — stride skew, gaps, guards.
+ * Dequantised value = e4m3(byte) * 2^(scale - 127).  The scale rows are PLAIN LINEAR: byte k of a scale
+ * row belongs to elements 32 k .. 32 k + 31 of the element row.  The swizzled scale layouts particular
+ * MFMA kernels want are the consumer's business.
+ * CHECKS, all before any HIP call (a refused call writes nothing).  The plan, count, sizes, overflow
+ * and the 2^31 - 1 tile cap follow the fp32 shard calls.  ALLRED_ERR_ARG: a NULL rows, scales or shard;
+ * rows or shard not 16-byte aligned, scales not 8-byte aligned; elems_per_rank == 0 or not a multiple
+ * of 8 total; row_stride < elems_per_rank or % 16 != 0; scale_stride < elems_per_rank / 32 or % 8 != 0;
+ * shard_stride < blk or % 4 != 0; address arithmetic that would overflow; a flag bit other than
+ * ALLRED_MX_SCALE_RCEIL.  ALLRED_ERR_UNSUPPORTED, for the WHOLE list: a bucket that is not whole tiles
+ * (total < 8 or elems_per_rank % (256 * total) != 0).  count == 0: ALLRED_OK, nothing launched.
+ * DISJOINTNESS (csrc/mx_ranges.hpp; byte-exact and block-exact, else ALLRED_ERR_ARG): per bucket the
+ * element rows are ONE interval [rows, rows + total * row_stride), the scale rows ONE interval
+ * [scales, scales + total * scale_stride), the shard `total` separate block intervals of blk floats;
+ * all pairwise disjoint, within a bucket and across buckets.  Rows or scales may sit in the gap of a
+ * wide shard_stride.
+ * LAUNCHES: a per-bucket table entry carries two more words than the fp32 call's, so ONE launch covers
+ * ALLRED_MX_GROUP_MAX = 32 buckets (3088 bytes of kernel arguments, below 4 KiB), in list order:
+ * allred_plan_all_gather_shards_mxfp8_launches returns ceil(count / 32), or a negative status for
+ * arguments the call would refuse.  The tables travel by value, so the call can be captured into a
+ * graph.  One kernel form, no routing rule and no tune key; pipe_grid caps the grid like every
+ * persistent pass. */
+#define ALLRED_MX_GROUP_MAX 32          /* buckets one launch covers */
+#define ALLRED_MX_SCALE_RCEIL 1         /* flags bit 0; without it: the OCP floor rule */
+typedef struct {                        /* 56 bytes */
+    uint8_t*  rows;                     /* e4m3fn bytes, rank r's row at rows + r * row_stride, WRITTEN */
+    uint64_t  row_stride;               /* bytes; >= elems_per_rank, % 16 == 0 */
+    uint8_t*  scales;                   /* E8M0 bytes, rank r's at scales + r * scale_stride, WRITTEN */
+    uint64_t  scale_stride;             /* bytes; >= elems_per_rank / 32, % 8 == 0 */
+    uint64_t  elems_per_rank;
+    const float* shard;                 /* as allred_shard_bucket_f32: block b at shard + b * shard_stride */
+    uint64_t  shard_stride;             /* floats; >= blk, % 4 == 0 */
+} allred_mx_bucket_f32;
+int allred_plan_all_gather_shards_mxfp8(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                        void* stream);
+int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -33,7 +33,7 @@ __all__ = [
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
-    "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX",
+    "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX", "mxfp8_dequantize",
 ]
 
 
@@ -210,6 +210,25 @@ def adamw_hyper_groups(groups, step: int = 1, max_norm: float = float("inf")) ->
         raise ValueError(f"1 .. {ADAMW_PARAM_GROUPS_MAX} parameter groups, not {len(groups)}")
     keys = ("lr", "betas", "eps", "weight_decay")
     return np.stack([adamw_hyper(**{k: g[k] for k in keys if k in g}, step=step, max_norm=max_norm) for g in groups])
+
+
+def mxfp8_dequantize(elements_u8, scales_u8) -> np.ndarray:
+    """What Plan.all_gather_shards_mxfp8 wrote, as float32: e4m3fn(byte) * 2^(scale - 127), the scale of
+    element k being scales_u8[..., k // 32].  elements_u8: (..., n) uint8, n % 32 == 0; scales_u8:
+    (..., n / 32) uint8.  NaN for the element byte 0x7F / 0xFF and for every element under a 0xFF scale.
+    Exact — every product is a float32, denormals included — with one exception: under rceil a block whose
+    amax is within half an e4m3 step of 2^128 holds the element 256 at scale 2^120, which is +-Inf here."""
+    e = np.asarray(elements_u8, dtype=np.uint8)
+    s = np.asarray(scales_u8, dtype=np.uint8)
+    if e.shape[-1] % 32 or s.shape != e.shape[:-1] + (e.shape[-1] // 32,):
+        raise ValueError(f"elements {e.shape} and scales {s.shape} do not belong together")
+    exp, man = ((e >> 3) & 0xF).astype(np.int32), (e & 7).astype(np.float64)
+    mag = np.where(exp == 0, man * 2.0 ** -9, (1.0 + man / 8.0) * np.exp2((exp - 7).astype(np.float64)))
+    val = np.where(e & 0x80, -mag, mag)
+    val = np.where((e & 0x7F) == 0x7F, np.nan, val)
+    scale = np.where(s == 0xFF, np.nan, np.exp2(s.astype(np.float64) - 127.0))
+    with np.errstate(over="ignore"):
+        return (val * np.repeat(scale, 32, axis=-1)).astype(np.float32)
 
 
 # ---------------------------------------------------------------- device
@@ -449,6 +468,35 @@ class Plan:
         st = lib.allred_plan_adamw_shards_f32_launches(self._h, arr, count)
         if st < 0:
             raise AllredError(st, "plan_adamw_shards_f32_launches")
+        return st
+
+    @staticmethod
+    def _mx_buckets_f32(buckets):
+        """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, elems_per_rank, shard_ptr, shard_stride) —
+        e4m3 element rows and E8M0 scale rows with strides in bytes, an fp32 shard with its stride in floats —
+        as an allred_mx_bucket_f32 array (None when empty)"""
+        items = [(int(rows) if rows else None, int(rs), int(scales) if scales else None, int(ss), int(n),
+                  int(shard) if shard else None, int(shard_stride))
+                 for rows, rs, scales, ss, n, shard, shard_stride in buckets]
+        return ((_lib.MxBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def all_gather_shards_mxfp8(self, buckets, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp8: block b of the fp32 shard quantised to OCP MXFP8 — e4m3fn
+        bytes into block b of every rank's element row, one E8M0 scale byte per 32 elements into every
+        rank's scale row — for every bucket of the list, one launch per ALLRED_MX_GROUP_MAX buckets; the
+        shards are only read.  rceil: the scale exponent rounded up (no finite element saturates)
+        instead of the OCP floor rule.  mxfp8_dequantize gives the values back."""
+        arr, count = self._mx_buckets_f32(buckets)
+        flags = _lib.MX_SCALE_RCEIL if rceil else 0
+        check(lib.allred_plan_all_gather_shards_mxfp8(self._h, arr, count, flags, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp8")
+
+    def shards_mxfp8_launches(self, buckets) -> int:
+        """Kernel launches all_gather_shards_mxfp8 would enqueue for the list: one per ALLRED_MX_GROUP_MAX buckets."""
+        arr, count = self._mx_buckets_f32(buckets)
+        st = lib.allred_plan_all_gather_shards_mxfp8_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_all_gather_shards_mxfp8_launches")
         return st
 
     def rank_zones(self, stamps: np.ndarray):

@@ -163,6 +163,15 @@ ADAMW_ZERO_GRAD = 1    # ALLRED_ADAMW_ZERO_GRAD: its flags bit 0
 ADAMW_PARAM_GROUPS_MAX = 8   # ALLRED_ADAMW_PARAM_GROUPS_MAX: hyper sets one allred_plan_adamw_all_gather_shards_f32_groups takes
 
 
+class MxBucketF32(C.Structure):   # allred_mx_bucket_f32: e4m3 element rows, E8M0 scale rows (strides in bytes), the fp32 shard (floats)
+    _fields_ = [("rows", C.c_void_p), ("row_stride", C.c_uint64), ("scales", C.c_void_p), ("scale_stride", C.c_uint64),
+                ("elems_per_rank", C.c_uint64), ("shard", C.c_void_p), ("shard_stride", C.c_uint64)]
+
+
+MX_GROUP_MAX = 32     # ALLRED_MX_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8 covers
+MX_SCALE_RCEIL = 1    # ALLRED_MX_SCALE_RCEIL: its flags bit 0
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -222,6 +231,8 @@ SIGNATURES = [
     ("allred_plan_adamw_shards_f32_launches", C.c_int, [_P, C.POINTER(AdamwBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_f32_groups", C.c_int,
      [_P, C.POINTER(AdamwBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_mxfp8", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -33,6 +33,7 @@
 #include "device_guard.hpp"
 #include "internal.hpp"
 #include "adamw_ranges.hpp"
+#include "mx_ranges.hpp"
 #include "shard_f32_norm_ranges.hpp"
 #include "shard_f32_ranges.hpp"
 #include "shard_ranges.hpp"
@@ -1025,9 +1026,47 @@ int adamw_check(const allred_plan* p, const allred_adamw_bucket_f32* buckets, in
     }
 }
 
+// The checks of allred_plan_all_gather_shards_mxfp8, all before any HIP call: the flags; the plan and
+// the count as shards_f32_check has them; then mx_ranges.hpp's rules for the list — pointers,
+// alignments, sizes, strides, the tile cap, the disjointness of element rows, scale rows and shard
+// blocks (which also refuses address arithmetic that would overflow), and the one kernel form's shape.
+static_assert(kMxMaxTiles == kTileSpanMaxTiles, "mx_ranges.hpp's copy of tile_span.hpp's constant");
+int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags) {
+    if (!mx_flags_ok(flags)) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count == 0) return ALLRED_OK;
+    if (!buckets) return ALLRED_ERR_ARG;
+    std::vector<MxRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_mx_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = MxRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.elems_per_rank, b.shard, b.shard_stride};
+    }
+    switch (mx_list_verdict(ranges.data(), count, (uint64_t)p->total)) {
+        case kMxOk: return ALLRED_OK;
+        case kMxUnsupported: return ALLRED_ERR_UNSUPPORTED;
+        default: return ALLRED_ERR_ARG;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int allred_plan_all_gather_shards_mxfp8(allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                        void* stream) {
+    const int st = mx_check(p, buckets, count, flags);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp8(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, /*dry=*/false, stream);
+}
+
+int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* p, const allred_mx_bucket_f32* buckets, int count) {
+    const int st = mx_check(p, buckets, count, 0);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_ag_group_mxfp8(buckets, count, p->total, false, /*dry=*/true, nullptr);
+}
 
 int allred_plan_reduce_scatter_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {
     return shards_run(p, buckets, count, ALLRED_OP_REDUCE_SCATTER, stream);

@@ -124,6 +124,10 @@ int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, int count, in
 int launch_adamw_groups_f32(const allred_adamw_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                             const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                             void* stream);
+// a list of (checked) whole-tile buckets with an fp32 shard, e4m3 element rows and E8M0 scale rows
+// (mx_kernels.hip): the shard quantised to MXFP8 into every rank's rows — k_ag_group_mxfp8 —,
+// ALLRED_MX_GROUP_MAX buckets per launch.  rceil: ALLRED_MX_SCALE_RCEIL.  dry: as above.
+int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
