@@ -595,7 +595,7 @@ int allred_plan_adamw_shards_f32_launches(const allred_plan* plan, const allred_
  * 16-byte aligned, only read, rewritten by the caller between graph replays like the one set);
  * group_of is a HOST array of count bytes, read during the call only: bucket i uses
  * hyper[group_of[i]].  group_of == NULL: every bucket is in group 0.  The kernel traces as
- * k_adamw_ag_groups_f32<P, false|true> (csrc/adamw_groups_kernels.hip), ALSO for ngroups == 1: the
+ * k_adamw_ag_groups_f32<P, false|true> (csrc/adamw_kernels.hip), ALSO for ngroups == 1: the
  * call has one kernel form, no routing rule and no tune key.  No reference counterpart.
  * SEMANTICS: those of allred_plan_adamw_all_gather_shards_f32 above, with two changes.
  *   CALL-WIDE: N, skip and c are ONE value for the whole call — gradient clipping is by the global

@@ -1,6 +1,7 @@
 // device.hpp — CDNA4 (gfx950) device helpers shared by the engine's kernels
-// (kernels.hip: virtual-rank plans; peer_kernels.hip: across GPUs) and by the
-// micro-benchmarks under tools/ubench/.
+// (kernels.hip: virtual-rank plans; shard_f32_kernels.hip, adamw_kernels.hip,
+// mx_kernels.hip: the fp32-shard calls; peer_kernels.hip: across GPUs) and by
+// the micro-benchmarks under tools/ubench/.
 //
 // bf16 arithmetic: unpack to fp32 (<< 16), add in fp32, pack back with the
 // gfx950 v_cvt_pk_bf16_f32 (round to nearest even) — one rounding per add, the
@@ -283,6 +284,43 @@ __device__ __forceinline__ uint32_t order_byte_load(const uint8_t* order, int la
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// ---------------------------------------------------------------------------
+// What the fp32-shard kernels share (shard_f32_kernels.hip, adamw_kernels.hip,
+// mx_kernels.hip): the 64-lane fp32 sum in index order.
+// ---------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// lanes l and l ^ 32 of a wave: lower half's value + upper half's, in both lanes.  gfx950's
+// v_permlane32_swap exchanges the upper 32 lanes of one register with the lower 32 of another: of
+// two copies of x it makes the lower half's values in all 64 lanes and the upper half's in all 64.
+__device__ __forceinline__ float add_halves(float x) {
+#if __has_builtin(__builtin_amdgcn_permlane32_swap)
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+#else
+    return x + __shfl_xor(x, 32);
+#endif
+}
+
+// x + the x of the lane a DPP control names: a register move, no trip through the LDS crossbar
+template <int CTRL>
+__device__ __forceinline__ float add_dpp(float x) {
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
+}
+
+// Five levels of a balanced tree over the 32 lanes of each wave half, in lane order (level k adds
+// adjacent groups of 2^k lanes), as a butterfly: every lane ends with its half's sum.  An fp32 add
+// is commutative, so which of the two siblings a lane reads first does not show in the bits.
+// Every lane of the wave must be active.  add_halves(add_lanes32(x)): the balanced tree over the
+// wave's 64 values in index order.
+__device__ __forceinline__ float add_lanes32(float t) {
+    t = add_dpp<0xB1>(t);    // quad_perm [1, 0, 3, 2]: lane ^ 1
+    t = add_dpp<0x4E>(t);    // quad_perm [2, 3, 0, 1]: lane ^ 2
+    t = add_dpp<0x141>(t);   // row_half_mirror: a lane of the other quad of the 8, all four of which hold that quad's sum
+    t = add_dpp<0x140>(t);   // row_mirror: likewise the other 8 of the 16
+    return t + __shfl_xor(t, 16);
+}
 
 // bounded waits of the peer kernels: a wait gives up after kPeerWaitTicks of
 // the 100 MHz s_memrealtime clock (4 s, far above any legitimate skew between

@@ -1119,8 +1119,8 @@ int allred_plan_adamw_all_gather_shards_f32(allred_plan* p, const allred_adamw_b
     if (st != ALLRED_OK || count == 0) return st;
     DeviceGuard guard(p->desc.device);
     if (!guard.ok) return ALLRED_ERR_HIP;
-    return launch_adamw_group_f32(buckets, count, p->total, hyper, norm_sq, info, (flags & ALLRED_ADAMW_ZERO_GRAD) != 0,
-                                  /*dry=*/false, stream);
+    return launch_adamw_group_f32(buckets, nullptr, count, p->total, hyper, /*ngroups=*/0, norm_sq, info,
+                                  (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, /*dry=*/false, stream);
 }
 
 // The group rules first (adamw_ranges.hpp adamw_groups_ok: ngroups, every group index), then
@@ -1134,14 +1134,15 @@ int allred_plan_adamw_all_gather_shards_f32_groups(allred_plan* p, const allred_
     if (st != ALLRED_OK || count == 0) return st;
     DeviceGuard guard(p->desc.device);
     if (!guard.ok) return ALLRED_ERR_HIP;
-    return launch_adamw_groups_f32(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
-                                   (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, stream);
+    return launch_adamw_group_f32(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                  (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, /*dry=*/false, stream);
 }
 
 int allred_plan_adamw_shards_f32_launches(const allred_plan* p, const allred_adamw_bucket_f32* buckets, int count) {
     const int st = adamw_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true);
     if (st != ALLRED_OK || count == 0) return st;
-    return launch_adamw_group_f32(buckets, count, p->total, nullptr, nullptr, nullptr, false, /*dry=*/true, nullptr);
+    return launch_adamw_group_f32(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/0, nullptr, nullptr, false, /*dry=*/true,
+                                  nullptr);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -115,15 +115,13 @@ int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, in
                            float scale, bool accumulate, bool dry, void* stream, float* norm_sq = nullptr,
                            void* norm_ws = nullptr);
 // a list of (checked) whole-tile buckets with their four fp32 planes (adamw_kernels.hip): the clipped AdamW
-// step of allred.h on the planes and p' rounded once to bf16 into every rank row — k_adamw_ag_group_f32 —,
-// ALLRED_ADAMW_GROUP_MAX buckets per launch; info goes to the first launch alone.  dry: as above.
-int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, int count, int total, const allred_adamw_hyper* hyper,
-                           const float* norm_sq, float* info, bool zero_grad, bool dry, void* stream);
-// the same list with a parameter group per bucket (adamw_groups_kernels.hip; group_of == nullptr: group 0) and
-// hyper an array of ngroups sets — k_adamw_ag_groups_f32 —, the same 32 buckets per launch in list order
-int launch_adamw_groups_f32(const allred_adamw_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
-                            const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
-                            void* stream);
+// step of allred.h on the planes and p' rounded once to bf16 into every rank row, ALLRED_ADAMW_GROUP_MAX
+// buckets per launch in list order; info goes to the first launch alone.  ngroups == 0: hyper is one set —
+// k_adamw_ag_group_f32.  ngroups >= 1: hyper is an array of ngroups sets and group_of the buckets' parameter
+// groups (nullptr: group 0) — k_adamw_ag_groups_f32.  dry: as above.
+int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                           const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                           bool dry, void* stream);
 // a list of (checked) whole-tile buckets with an fp32 shard, e4m3 element rows and E8M0 scale rows
 // (mx_kernels.hip): the shard quantised to MXFP8 into every rank's rows — k_ag_group_mxfp8 —,
 // ALLRED_MX_GROUP_MAX buckets per launch.  rceil: ALLRED_MX_SCALE_RCEIL.  dry: as above.

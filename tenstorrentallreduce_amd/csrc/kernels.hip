@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "device.hpp"
+#include "group_batch.hpp"
 #include "group_span.hpp"
 #include "launch_util.hpp"
 #include "tile_span.hpp"
@@ -2112,20 +2113,20 @@ int launch_tree_group(const allred_bucket* buckets, int count, int total, int al
                       bool write_all, bool dry, void* stream) {
     const int64_t form = fused_form();
     hipStream_t st = (hipStream_t)stream;
-    GroupIn in[kGroupMax];
-    int pending = 0, launches = 0;
-    uint64_t pending_tiles = 0;
-    auto flush = [&]() -> int {
-        if (!pending) return ALLRED_OK;
-        ++launches;
-        const int members = pending;
-        const uint64_t tiles = pending_tiles;
-        pending = 0;
-        pending_tiles = 0;
-        if (dry) return ALLRED_OK;
-        const unsigned grid = persistent_grid(tiles, 512);
-        GroupSpan span;
-        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+    struct {} none;   // no side table
+    auto add = [&](int i, int) {
+        const allred_bucket& b = buckets[i];
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
+        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
+        if (whole_tiles && !lag64 && form != 1 && form != 2) return BatchAdd::member(GroupIn{b.ranks, b.rank_stride, tiles, bv / 32});
+        int s = ALLRED_OK;
+        if (!dry)
+            s = write_all ? launch_tree_fused(b.ranks, b.rank_stride, b.elems_per_rank, total, order, stream)
+                          : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, nullptr, 0, stream);
+        return BatchAdd::routed(s, write_all ? (int)fused_launches(ALLRED_BO, false, algo, side, b.elems_per_rank, total) : 1);
+    };
+    auto launch = [&](const GroupSpan& span, unsigned grid, int, uint64_t) {
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             if (write_all) hipLaunchKernelGGL((k_tree_group<p(), true>), dim3(grid), dim3(kBlock), 0, st, order, span);
             else hipLaunchKernelGGL((k_tree_group<p(), false>), dim3(grid), dim3(kBlock), 0, st, order, span);
@@ -2133,28 +2134,7 @@ int launch_tree_group(const allred_bucket* buckets, int count, int total, int al
         });
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
     };
-    for (int i = 0; i < count; ++i) {
-        const allred_bucket& b = buckets[i];
-        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
-        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
-        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
-        int s = ALLRED_OK;
-        if (whole_tiles && !lag64 && form != 1 && form != 2) {
-            in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
-            pending_tiles += tiles;
-            if (pending == kGroupMax) s = flush();
-        } else {
-            launches += write_all ? (int)fused_launches(ALLRED_BO, false, algo, side, b.elems_per_rank, total) : 1;
-            if (!dry)
-                s = write_all ? launch_tree_fused(b.ranks, b.rank_stride, b.elems_per_rank, total, order, stream)
-                              : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, nullptr, 0,
-                                                      stream);
-        }
-        if (s != ALLRED_OK) return s;
-    }
-    const int s = flush();
-    if (s != ALLRED_OK) return s;
-    return dry ? launches : ALLRED_OK;
+    return group_batch<kGroupMax>(count, dry, none, add, [](uint64_t tiles) { return persistent_grid(tiles, 512); }, launch);
 }
 
 // A list of buckets, each in place or with a shard buffer, through the reduce-scatter
@@ -2174,26 +2154,31 @@ int launch_shard_group(const allred_shard_bucket* buckets, int count, int total,
     const int64_t form = fused_form();
     const bool gather = op == ALLRED_OP_ALL_GATHER;
     hipStream_t st = (hipStream_t)stream;
-    GroupIn in[kGroupMax];
-    GroupShards shards{};
-    int pending = 0, launches = 0;
-    uint64_t pending_tiles = 0;
-    bool pending_shard = false;
-    auto flush = [&]() -> int {
-        if (!pending) return ALLRED_OK;
-        ++launches;
-        const int members = pending;
-        const uint64_t tiles = pending_tiles;
-        const bool with_shards = pending_shard;
-        pending = 0;
-        pending_tiles = 0;
-        pending_shard = false;
-        if (dry) return ALLRED_OK;
-        // the tree pass on 2 workgroups per CU like every tree pass; the copy, which holds no LDS, on
-        // up to kAgGroupGrid workgroups (measured against 512 and 2048: DESIGN.md §12)
-        const unsigned grid = persistent_grid(tiles, gather ? kAgGroupGrid : 512);
-        GroupSpan span;
-        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+    struct Side {
+        GroupShards shards;
+        bool any;   // a pending member has a shard
+    } side{};
+    auto add = [&](int i, int slot) {
+        const allred_shard_bucket& b = buckets[i];
+        if (total == 1 && !b.shard) return BatchAdd::routed(ALLRED_OK, 0);   // one rank owns its one block already
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
+        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
+        if (whole_tiles && !lag64 && form != 1 && form != 2) {
+            side.shards.s[slot] = GroupShard{b.shard, b.shard ? b.shard_stride : 0};
+            side.any = side.any || b.shard;
+            return BatchAdd::member(GroupIn{b.ranks, b.rank_stride, tiles, bv / 32});
+        }
+        int s = ALLRED_OK;
+        if (!dry)
+            s = gather ? launch_all_gather(b.ranks, b.rank_stride, b.elems_per_rank, total, b.shard, b.shard_stride, stream)
+                       : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, b.shard, b.shard_stride,
+                                               stream);
+        return BatchAdd::routed(s, 1);
+    };
+    auto launch = [&](const GroupSpan& span, unsigned grid, int, uint64_t) {
+        const GroupShards& shards = side.shards;
+        const bool with_shards = side.any;
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             if (gather) hipLaunchKernelGGL((k_ag_group<p()>), dim3(grid), dim3(kBlock), 0, st, span, shards);
             else if (with_shards)
@@ -2203,35 +2188,12 @@ int launch_shard_group(const allred_shard_bucket* buckets, int count, int total,
             if (gather) trace_launch(grid, kBlock, "k_ag_group<%d>", total);
             else trace_launch(grid, kBlock, with_shards ? "k_tree_group<%d, false, GroupShards>" : "k_tree_group<%d, false>", total);
         });
-        shards = GroupShards{};
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
     };
-    for (int i = 0; i < count; ++i) {
-        const allred_shard_bucket& b = buckets[i];
-        if (total == 1 && !b.shard) continue;   // one rank owns its one block already
-        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
-        const bool whole_tiles = total >= 8 && nv % 32 == 0 && bv % 32 == 0;
-        const bool lag64 = whole_tiles && total == 64 && form == 0 && tiles >= 1024;
-        int s = ALLRED_OK;
-        if (whole_tiles && !lag64 && form != 1 && form != 2) {
-            shards.s[pending] = GroupShard{b.shard, b.shard ? b.shard_stride : 0};
-            in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
-            pending_tiles += tiles;
-            pending_shard = pending_shard || b.shard;
-            if (pending == kGroupMax) s = flush();
-        } else {
-            ++launches;
-            if (!dry)
-                s = gather ? launch_all_gather(b.ranks, b.rank_stride, b.elems_per_rank, total, b.shard, b.shard_stride,
-                                               stream)
-                           : launch_reduce_scatter(b.ranks, b.rank_stride, b.elems_per_rank, total, order, b.shard,
-                                                   b.shard_stride, stream);
-        }
-        if (s != ALLRED_OK) return s;
-    }
-    const int s = flush();
-    if (s != ALLRED_OK) return s;
-    return dry ? launches : ALLRED_OK;
+    // the tree pass on 2 workgroups per CU like every tree pass; the copy, which holds no LDS, on
+    // up to kAgGroupGrid workgroups (measured against 512 and 2048: DESIGN.md §12)
+    return group_batch<kGroupMax>(count, dry, side, add,
+                                  [&](uint64_t tiles) { return persistent_grid(tiles, gather ? kAgGroupGrid : 512); }, launch);
 }
 
 int launch_tree_bcast_x(uint16_t* cur, uint16_t* prev, uint64_t stride, size_t n, int total, const uint8_t* order,

@@ -1,5 +1,4 @@
-// launch_util.hpp — what the launchers of every kernel file share (kernels.hip,
-// shard_f32_kernels.hip): the HIP status of a launch, the rank count as a
+// launch_util.hpp — what the launchers of every kernel file share: the HIP status of a launch, the rank count as a
 // template argument, the grid of a persistent pass.  Host code only.
 #pragma once
 

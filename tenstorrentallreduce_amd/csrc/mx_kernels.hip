@@ -7,21 +7,18 @@
 //                                a tile's 256 floats become 256 element bytes and 8 scale bytes,
 //                                written to every rank's element row and scale row.
 //
-// A translation unit of its own, like the AdamW files: the older objects stay what they were (same
-// code, same resources).  The scaling is ONE fp32 multiply by a power of two with denormals kept
-// (the build does not flush them), everything around it integer work: allred.h states every output
-// bit as a function of the input bits and the tests compare whole buffers.
+// The scaling is ONE fp32 multiply by a power of two with denormals kept (the build does not flush
+// them), everything around it integer work: allred.h states every output bit as a function of the
+// input bits and the tests compare whole buffers.
 #include <type_traits>
 
 #include "device.hpp"
+#include "group_batch.hpp"
 #include "group_span.hpp"
 #include "launch_util.hpp"
 
 namespace tsa {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMxGroupMax = ALLRED_MX_GROUP_MAX;   // buckets of one launch
 
@@ -44,7 +41,7 @@ static_assert(sizeof(GroupSpan) + sizeof(MxShards) < 4096, "kernel arguments sta
 static_assert(kMxGroupMax <= kGroupMax, "GroupSpan's table holds a launch");
 static_assert(sizeof(allred_mx_bucket_f32) == 56, "allred.h's layout");
 
-// max(x, the x of the lane a DPP control names), as unsigned integers: a register move, no LDS crossbar
+// max(x, the x of the lane a DPP control names), as unsigned integers: add_dpp's idiom (device.hpp)
 template <int CTRL>
 __device__ __forceinline__ uint32_t max_dpp(uint32_t x) {
     const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
@@ -178,44 +175,24 @@ constexpr uint64_t kAgGroupMxGrid = kMaxGrid;
 // last member is reached.  dry: nothing is launched and the number of launches is returned.
 int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    GroupIn in[kMxGroupMax];
     MxShards shards{};
-    int pending = 0, launches = 0;
-    uint64_t pending_tiles = 0;
-    auto flush = [&]() -> int {
-        if (!pending) return ALLRED_OK;
-        ++launches;
-        const int members = pending;
-        const uint64_t tiles = pending_tiles;
-        pending = 0;
-        pending_tiles = 0;
-        if (dry) return ALLRED_OK;
-        const unsigned grid = persistent_grid(tiles, kAgGroupMxGrid);
-        GroupSpan span;
-        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
+    auto add = [&](int i, int slot) {
+        const allred_mx_bucket_f32& b = buckets[i];
+        const uint64_t tiles = b.elems_per_rank / 256;
+        if (total < 8 || b.elems_per_rank % (256 * (uint64_t)total)) return BatchAdd::error(ALLRED_ERR_UNSUPPORTED);   // the caller's check, kept next to its use
+        shards.s[slot] = MxShard{b.shard, b.shard_stride, b.scales, b.scale_stride};
+        return BatchAdd::member(GroupIn{reinterpret_cast<uint16_t*>(b.rows), b.row_stride, tiles, tiles / total});
+    };
+    auto launch = [&](const GroupSpan& span, unsigned grid, int, uint64_t) {
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             if (rceil) hipLaunchKernelGGL((k_ag_group_mxfp8<p(), true>), dim3(grid), dim3(kBlock), 0, st, span, shards);
             else hipLaunchKernelGGL((k_ag_group_mxfp8<p(), false>), dim3(grid), dim3(kBlock), 0, st, span, shards);
             trace_launch(grid, kBlock, "k_ag_group_mxfp8<%d, %s>", total, tf(rceil));
         });
-        shards = MxShards{};
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
     };
-    for (int i = 0; i < count; ++i) {
-        const allred_mx_bucket_f32& b = buckets[i];
-        const uint64_t tiles = b.elems_per_rank / 256;
-        if (total < 8 || b.elems_per_rank % (256 * (uint64_t)total)) return ALLRED_ERR_UNSUPPORTED;   // the caller's check, kept next to its use
-        shards.s[pending] = MxShard{b.shard, b.shard_stride, b.scales, b.scale_stride};
-        in[pending++] = GroupIn{reinterpret_cast<uint16_t*>(b.rows), b.row_stride, tiles, tiles / total};
-        pending_tiles += tiles;
-        if (pending == kMxGroupMax) {
-            const int s = flush();
-            if (s != ALLRED_OK) return s;
-        }
-    }
-    const int s = flush();
-    if (s != ALLRED_OK) return s;
-    return dry ? launches : ALLRED_OK;
+    return group_batch<kMxGroupMax>(count, dry, shards, add, [](uint64_t tiles) { return persistent_grid(tiles, kAgGroupMxGrid); },
+                                    launch);
 }
 
 }  // namespace tsa

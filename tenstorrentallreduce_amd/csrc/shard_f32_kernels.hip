@@ -14,22 +14,20 @@
 //                              shard rounded ONCE to bf16 (pack_rne) and
 //                              written to every rank row.
 //
-// A translation unit of its own: kernels.hip's kernels and launch sites are
-// what tests/route_cases.py tabulates, and the bf16 engine's objects stay what
-// they were (same code, same resources).  The arithmetic here depends on the
-// build's -ffp-contract=off (Makefile, HIPFLAGS): `old + s * scale` must be one
-// fp32 multiply and one fp32 add, never an fma — allred.h states the result as
-// those two operations and the tests compare bits.
+// The arithmetic here depends on the build's -ffp-contract=off (Makefile,
+// HIPFLAGS): `old + s * scale` must be one fp32 multiply and one fp32 add, never
+// an fma — allred.h states the result as those two operations and the tests
+// compare bits.
 #include <type_traits>
 
 #include "device.hpp"
+#include "group_batch.hpp"
 #include "group_span.hpp"
 #include "launch_util.hpp"
 
 namespace tsa {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) f32x4 global_f32x4;
 
 // The fp32 shard buffers of a grouped launch: entry i for bucket i of the launch, block b of
@@ -91,36 +89,6 @@ __device__ __forceinline__ void tree_levels_f32(F8 (&x)[N]) {
     for (int s = 1; s < N; s *= 2)
 #pragma unroll
         for (int i = 0; i < N; i += 2 * s) x[i] = add8f(x[i], x[i + s]);
-}
-
-// lanes l and l ^ 32 of a wave: lower half's value + upper half's, in both lanes.  gfx950's
-// v_permlane32_swap exchanges the upper 32 lanes of one register with the lower 32 of another: of
-// two copies of x it makes the lower half's values in all 64 lanes and the upper half's in all 64.
-__device__ __forceinline__ float add_halves(float x) {
-#if __has_builtin(__builtin_amdgcn_permlane32_swap)
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-#else
-    return x + __shfl_xor(x, 32);
-#endif
-}
-
-// x + the x of the lane a DPP control names: a register move, no trip through the LDS crossbar
-template <int CTRL>
-__device__ __forceinline__ float add_dpp(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
-}
-
-// Five levels of a balanced tree over the 32 lanes of each wave half, in lane order (level k adds
-// adjacent groups of 2^k lanes), as a butterfly: every lane ends with its half's sum.  An fp32 add
-// is commutative, so which of the two siblings a lane reads first does not show in the bits.
-// Every lane of the wave must be active.
-__device__ __forceinline__ float add_lanes32(float t) {
-    t = add_dpp<0xB1>(t);    // quad_perm [1, 0, 3, 2]: lane ^ 1
-    t = add_dpp<0x4E>(t);    // quad_perm [2, 3, 0, 1]: lane ^ 2
-    t = add_dpp<0x141>(t);   // row_half_mirror: a lane of the other quad of the 8, all four of which hold that quad's sum
-    t = add_dpp<0x140>(t);   // row_mirror: likewise the other 8 of the 16
-    return t + __shfl_xor(t, 16);
 }
 
 // A wave's share of a tile's tree, as tree_wave_part: this lane's LPL adjacent leaves ord[0 .. LPL)
@@ -482,25 +450,16 @@ int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, in
     const bool gather = op == ALLRED_OP_ALL_GATHER;
     if (gather && norm_sq) return ALLRED_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    GroupIn in[kGroupMax];
     GroupShardsF32 shards{};
-    int pending = 0, launches = 0;
-    uint64_t pending_tiles = 0, launched_tiles = 0;
-    auto flush = [&]() -> int {
-        if (!pending) return ALLRED_OK;
-        ++launches;
-        const int members = pending;
-        const uint64_t tiles = pending_tiles;
-        pending = 0;
-        pending_tiles = 0;
-        if (dry) return ALLRED_OK;
-        // the tree pass on 2 workgroups per CU like every tree pass (LDS-bound); the copy, which
-        // holds no LDS, on up to kAgGroupGrid workgroups like k_ag_group
-        const unsigned grid = persistent_grid(tiles, gather ? kAgGroupGrid : 512);
-        GroupSpan span;
-        if (!group_span_make(&span, in, members, grid)) return ALLRED_ERR_ARG;
-        const NormArgs na{norm_sq, norm_ws, (uint32_t)launched_tiles, (uint32_t)(launches - 1)};
-        launched_tiles += tiles;   // the list's tiles are below 2^31 (engine.cpp group_check)
+    auto add = [&](int i, int slot) {
+        const allred_shard_bucket_f32& b = buckets[i];
+        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
+        if (total < 8 || nv % 32 || bv % 32) return BatchAdd::error(ALLRED_ERR_UNSUPPORTED);   // the caller's check, kept next to its use
+        shards.s[slot] = GroupShardF32{b.shard, b.shard_stride};
+        return BatchAdd::member(GroupIn{b.ranks, b.rank_stride, tiles, bv / 32});
+    };
+    auto launch = [&](const GroupSpan& span, unsigned grid, int index, uint64_t tile_off) {
+        const NormArgs na{norm_sq, norm_ws, (uint32_t)tile_off, (uint32_t)index};
         const bool found = for_ranks<8, 64>(total, [&](auto p) {
             if (norm_sq) {
                 if (accumulate)
@@ -517,24 +476,12 @@ int launch_shard_group_f32(const allred_shard_bucket_f32* buckets, int count, in
             if (gather) trace_launch(grid, kBlock, "k_ag_group_f32<%d>", total);
             else trace_launch(grid, kBlock, "k_tree_group_f32<%d, %s>", total, tf(accumulate));
         });
-        shards = GroupShardsF32{};
         return found ? last_error() : ALLRED_ERR_UNSUPPORTED;
     };
-    for (int i = 0; i < count; ++i) {
-        const allred_shard_bucket_f32& b = buckets[i];
-        const uint64_t nv = b.elems_per_rank / 8, bv = nv / total, tiles = nv / 32;
-        if (total < 8 || nv % 32 || bv % 32) return ALLRED_ERR_UNSUPPORTED;   // the caller's check, kept next to its use
-        shards.s[pending] = GroupShardF32{b.shard, b.shard_stride};
-        in[pending++] = GroupIn{b.ranks, b.rank_stride, tiles, bv / 32};
-        pending_tiles += tiles;
-        if (pending == kGroupMax) {
-            const int s = flush();
-            if (s != ALLRED_OK) return s;
-        }
-    }
-    const int s = flush();
-    if (s != ALLRED_OK) return s;
-    return dry ? launches : ALLRED_OK;
+    // the tree pass on 2 workgroups per CU like every tree pass (LDS-bound); the copy, which
+    // holds no LDS, on up to kAgGroupGrid workgroups like k_ag_group
+    return group_batch<kGroupMax>(count, dry, shards, add,
+                                  [&](uint64_t tiles) { return persistent_grid(tiles, gather ? kAgGroupGrid : 512); }, launch);
 }
 
 }  // namespace tsa

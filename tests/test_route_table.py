@@ -85,6 +85,16 @@ def test_every_launch_site_feeds_the_trace():
             assert "trace_launch(" in window or "note_launch(" in window, f"kernels.hip:{i + 1}: launch without a trace record"
 
 
+def test_every_launch_site_of_the_shard_family_feeds_the_trace():
+    """the same for the fp32-shard files: their traces are what the grouped GPU tests pin"""
+    for name, at_least in (("shard_f32_kernels.hip", 5), ("adamw_kernels.hip", 4), ("mx_kernels.hip", 2)):
+        lines = open(os.path.join(CSRC, name)).read().splitlines()
+        sites = [i for i, line in enumerate(lines) if "hipLaunchKernelGGL(" in line]
+        assert len(sites) >= at_least, name
+        for i in sites:
+            assert "trace_launch(" in "\n".join(lines[i:i + 10]), f"{name}:{i + 1}: launch without a trace record"
+
+
 def test_cases_are_well_formed():
     ids = [c["id"] for c in route_cases.CASES]
     assert len(ids) == len(set(ids)) and len(ids) >= 150
