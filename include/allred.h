@@ -663,6 +663,20 @@ int allred_plan_adamw_all_gather_shards_f32_groups(
  * Dequantised value = e4m3(byte) * 2^(scale - 127).  The scale rows are PLAIN LINEAR: byte k of a scale
  * row belongs to elements 32 k .. 32 k + 31 of the element row.  The swizzled scale layouts particular
  * MFMA kernels want are the consumer's business.
+ * WHAT THE MI355X MAKES OF THE ROWS (tests/test_gpu_mx_consumer.py; tests/mx_consumer.hip is the consumer).
+ * The linear rows feed v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 on both sides) as they lie, with no byte
+ * repacked and no scale swizzled, under this lane map, established on exact integer data: lane l of a
+ * wave, g = l >> 4, loads of matrix row l & 15 the 16 bytes k0 + 16 g .. + 15 into dwords 0 .. 3 and the 16
+ * bytes k0 + 64 + 16 g .. + 15 into dwords 4 .. 7, and as its scale the byte at k0 / 32 + g of the row's
+ * linear scale row, which the instruction applies to bytes k0 + 32 g .. + 31.  So a lane's eight dwords are
+ * NOT one MX block: they are halves of two.  The hardware's reading of every element byte under scale
+ * bytes 0, 1, 8, 119, 127, 135, 246 and 254 is e4m3(byte) * 2^(scale - 127) as stated here — bias 127,
+ * subnormals, signs —; 0x7F, 0xFF and a 0xFF scale (over zeros too) make all sixteen outputs of their
+ * matrix row NaN and touch no other row.  A dequantised value in the fp32 denormal range is KEPT, not
+ * flushed; one that overflows fp32 (256 * 2^120 under RCEIL) comes out as +-Inf of its sign.  One
+ * instruction's sum over four differently scaled groups differed from the float64 product by up to
+ * 9.53e-6 = 2^-16.7 times sum |a_k b_k|: more than the 2^-17 that 128 fp32 adds allow, so the matrix core
+ * does not add as fp32 adds would.  The semantics above stood as written.
  * CHECKS, all before any HIP call (a refused call writes nothing).  The plan, count, sizes, overflow
  * and the 2^31 - 1 tile cap follow the fp32 shard calls.  ALLRED_ERR_ARG: a NULL rows, scales or shard;
  * rows or shard not 16-byte aligned, scales not 8-byte aligned; elems_per_rank == 0 or not a multiple

@@ -80,9 +80,11 @@ static void emit(bool swing, int side, int total, bool last) {
 int main() {
     // grids: the reference's square S x S (S = 1,2,4,8) and the rectangular
     // (S, N) mappings used for 2/4/8 GPUs; (8,16) is the known
-    // invalid rectangle (out-of-range RecDub partners) kept as a negative case.
+    // invalid rectangle (out-of-range RecDub partners) kept as a negative case,
+    // last, so that a new grid in front of it changes no line of an older one;
+    // (8,32) is the 8 x 4 grid every 32-rank GPU test runs.
     struct G { int side, total; };
-    const G grids[] = {{1, 1}, {2, 2}, {2, 4}, {4, 8}, {4, 16}, {8, 64}, {8, 16}};
+    const G grids[] = {{1, 1}, {2, 2}, {2, 4}, {4, 8}, {4, 16}, {8, 64}, {8, 32}, {8, 16}};
     const int ng = sizeof(grids) / sizeof(grids[0]);
     std::printf("{\"highest_power_of_two\": [");
     for (int v = -2; v <= 20; ++v) std::printf("%s[%d, %d]", v > -2 ? ", " : "", v, highest_power_of_two(v));

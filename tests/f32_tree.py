@@ -10,6 +10,13 @@ expect_shard(data, tree_order, scale, old)    (P, blk) float32: block b = tree b
                                               two separate float32 operations (no fma)
 bf16_rne(f32)                                 uint16: the integer rule (u + 0x7FFF + ((u >> 16) & 1)) >> 16;
                                               a NaN comes out as SOME NaN: compare NaNs by class (same_bf16)
+
+WHERE THE ORDER IS PINNED.  The callers pass t.schedule(...)["tree_order"], the table the product uploads and
+its kernels read.  tests/test_bo_tree.py holds that table to the reference on the CPU: the tree derived from
+the partners and receive masks of tests/golden/schedule_ref.json alone (tests/bo_tree.py) is, up to swapping
+the children of a node, the balanced pairing tree_sum applies to tree_order[b], for every grid the GPU tests
+run — the 8 x 4 grid of their 32-rank cases included — and for Swing-1D at 8 ranks; its float32 bits equal
+tree_sums', and with every add rounded to bf16 it is the CPU oracle's BO allreduce.
 """
 import numpy as np
 
