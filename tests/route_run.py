@@ -1,7 +1,7 @@
 """The route cases of tests/route_cases.py as runnable pieces (helper, no tests).
 
-PREPARE[op](c, kind, place) builds the buffers of case c on dataset `kind` and their expected images
-and returns a Prepared:
+PREPARE[op](c, kind, place, seed) builds the buffers of case c on dataset `kind` (of seed `seed`; the
+default is the images the route modules have always run on) and their expected images and returns a Prepared:
     prepare   every buffer the call may touch is sentinel-filled around its payload; the expected
               image is the CPU oracle where the operation defines a result, the input bits where it
               only reads, the sentinel everywhere else;
@@ -38,14 +38,14 @@ def frozen(a):
 
 
 @functools.lru_cache(maxsize=None)
-def dataset(kind, total, n):
-    return frozen(getattr(hard_inputs, kind)(total, n, SEED))
+def dataset(kind, total, n, seed=SEED):
+    return frozen(getattr(hard_inputs, kind)(total, n, seed))
 
 
 @functools.lru_cache(maxsize=None)
-def reference(kind, name, algo, side, total, n, acc16=False):
-    """the oracle's allreduce of dataset(kind, total, n): (total, n) uint16"""
-    want = [r.copy() for r in dataset(kind, total, n)]
+def reference(kind, name, algo, side, total, n, acc16=False, seed=SEED):
+    """the oracle's allreduce of dataset(kind, total, n, seed): (total, n) uint16"""
+    want = [r.copy() for r in dataset(kind, total, n, seed)]
     oracle.allreduce(name, algo, side, want, total, acc16=acc16)
     return frozen(np.stack(want))
 
@@ -275,10 +275,10 @@ class Prepared:
 
 
 # ------------------------------------------------------------------ the operations
-def prepare_allreduce(c, kind, place=NEAR):
+def prepare_allreduce(c, kind, place=NEAR, seed=SEED):
     total, n = c["total"], c["n"]
-    data = dataset(kind, total, n)
-    want = reference(kind, VARIANT_NAME[c["variant"]], c["algo"], c["side"], total, n, c["acc"] == route_cases.BF16)
+    data = dataset(kind, total, n, seed)
+    want = reference(kind, VARIANT_NAME[c["variant"]], c["algo"], c["side"], total, n, c["acc"] == route_cases.BF16, seed)
     rows = place.rank_rows("ranks", data, c["host"])
     plan = t.Plan(c["algo"], c["variant"], c["side"], n, total, c["exec"], mem_accum=c["acc"])
     ws = Workspace(plan.workspace_bytes)
@@ -290,11 +290,11 @@ def prepare_allreduce(c, kind, place=NEAR):
                     want[0] if holds else None)
 
 
-def prepare_reduce_scatter(c, kind, place=NEAR):
+def prepare_reduce_scatter(c, kind, place=NEAR, seed=SEED):
     total, n, compact = c["total"], c["n"], c["op"] == "rs_compact"
     blk = n // total
-    data = dataset(kind, total, n)
-    want = owner_blocks(reference(kind, "bo", c["algo"], c["side"], total, n), total, n)
+    data = dataset(kind, total, n, seed)
+    want = owner_blocks(reference(kind, "bo", c["algo"], c["side"], total, n, seed=seed), total, n)
     rows = place.rank_rows("ranks", data)
     out = place.side_rows("out", total, blk)
     plan = t.Plan(c["algo"], route_cases.BO, c["side"], n, total, route_cases.FUSED)
@@ -314,11 +314,11 @@ def prepare_reduce_scatter(c, kind, place=NEAR):
     return Prepared([rows, out], call, lambda: len(c["trace"]), plan)
 
 
-def prepare_all_gather(c, kind, place=NEAR):
+def prepare_all_gather(c, kind, place=NEAR, seed=SEED):
     """a copy: every 16-bit pattern must arrive as it is, so nothing is compared by class"""
     total, n, from_in = c["total"], c["n"], c["op"] == "ag_from_in"
     blk = n // total
-    data = dataset(kind, total, n)
+    data = dataset(kind, total, n, seed)
     rows = place.rank_rows("ranks", data)
     src = np.stack([data[(b + 1) % total, b * blk:(b + 1) * blk] for b in range(total)])   # not the owners' blocks
     din = place.side_rows("in", total, blk, src)
@@ -333,13 +333,13 @@ def prepare_all_gather(c, kind, place=NEAR):
     return Prepared([rows, din], call, lambda: len(c["trace"]), plan)
 
 
-def prepare_group(c, kind, place=NEAR):
+def prepare_group(c, kind, place=NEAR, seed=SEED):
     total, op = c["total"], c["op"]
     plan = t.Plan(c["algo"], route_cases.BO, c["side"], c["n"], total, route_cases.FUSED)
     bufs, shards, args = [], [], []
     for i, (n, has_shard) in enumerate(c["buckets"]):
         blk = n // total
-        data = dataset(kind, total, n)
+        data = dataset(kind, total, n, seed)
         where = place.bucket(c, i)
         rows = where.rank_rows(f"bucket {i} ranks", data)
         src = np.stack([data[(b + 1) % total, b * blk:(b + 1) * blk] for b in range(total)])
@@ -350,11 +350,11 @@ def prepare_group(c, kind, place=NEAR):
         args.append((rows.ptr, rows.width, n, shard.ptr, shard.width) if shard else (rows.ptr, rows.width, n))
         cols = columns(kind, total, n)
         if op == "group_exec":
-            rows.rows()[:, :n] = reference(kind, "bo", c["algo"], c["side"], total, n)
+            rows.rows()[:, :n] = reference(kind, "bo", c["algo"], c["side"], total, n, seed=seed)
             for r in range(total):
                 rows.plant(r, cols, 0, n)
         elif op in ("group_rs", "shard_rs"):
-            want = owner_blocks(reference(kind, "bo", c["algo"], c["side"], total, n), total, n)
+            want = owner_blocks(reference(kind, "bo", c["algo"], c["side"], total, n, seed=seed), total, n)
             for b in range(total):
                 if shard:
                     shard.rows()[b, :blk] = want[b]
@@ -385,14 +385,14 @@ def prepare_group(c, kind, place=NEAR):
     return Prepared(bufs + shards, call, dry, plan)
 
 
-def prepare_tree_bcast(c, kind, place=NEAR):
+def prepare_tree_bcast(c, kind, place=NEAR, seed=SEED):
     """tree 0 of `cur` over the whole vector to cur_out (= the LO value of rank 0), prev_src to every row of prev"""
     total, n = c["total"], c["n"]
-    data = dataset(kind, total, n)
-    want = reference(kind, "lo", c["algo"], c["side"], total, n)[0]
+    data = dataset(kind, total, n, seed)
+    want = reference(kind, "lo", c["algo"], c["side"], total, n, seed=seed)[0]
     cur = place.rank_rows("cur", data)
-    prev = place.rank_rows("prev", dataset("cancel" if kind == "nonfinite" else "nonfinite", total, n))
-    src_bits = np.random.default_rng(SEED + n).integers(0, 0x10000, n).astype(np.uint16)   # any pattern: a copy
+    prev = place.rank_rows("prev", dataset("cancel" if kind == "nonfinite" else "nonfinite", total, n, seed))
+    src_bits = np.random.default_rng(seed + n).integers(0, 0x10000, n).astype(np.uint16)   # any pattern: a copy
     src = place.side_rows("prev_src", 1, n, src_bits)
     out = place.side_rows("cur_out", 1, n)
     assert cur.width == prev.width
