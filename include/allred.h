@@ -52,6 +52,9 @@ extern "C" {
  * Still ABI 7: allred_mx_bucket_f32, ALLRED_MX_GROUP_MAX, ALLRED_MX_SCALE_RCEIL and
  * allred_plan_all_gather_shards_mxfp8 / allred_plan_all_gather_shards_mxfp8_launches are additions — the grouped
  * all-gather from fp32 shards into MXFP8 rows: e4m3 bytes and one E8M0 scale byte per 32 elements.
+ * Still ABI 7: allred_adamw_mx_bucket_f32, ALLRED_ADAMW_MX_GROUP_MAX, ALLRED_ADAMW_MX_RCEIL and
+ * allred_plan_adamw_all_gather_shards_mxfp8 / allred_plan_adamw_shards_mxfp8_launches are additions — the
+ * AdamW step with parameter groups inside the MXFP8 all-gather's launch: p' quantised where it is computed.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -709,6 +712,81 @@ typedef struct {                        /* 56 bytes */
 int allred_plan_all_gather_shards_mxfp8(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
                                         void* stream);
 int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
+/* ADAMW INSIDE THE MXFP8 ALL-GATHER: allred_plan_adamw_all_gather_shards_f32_groups with the rows of
+ * allred_plan_all_gather_shards_mxfp8 — the MXFP8 training step in TWO launches
+ * (allred_plan_reduce_scatter_shards_f32_norm, then this call), as the bf16 step is.  p' is quantised
+ * in the register it is computed in: no bf16 rows that nobody reads, no second pass over the masters.
+ * ONE entry point and ONE kernel form, always with parameter groups: ngroups = 1 with group_of = NULL
+ * is the one-set call.  hyper, group_of, ngroups, norm_sq and info are those of the groups call above;
+ * rows, row_stride, scales and scale_stride those of allred_mx_bucket_f32; the four planes and
+ * shard_stride those of allred_adamw_bucket_f32.  The kernel traces as
+ * k_adamw_ag_mxfp8<P, false|true, false|true> (csrc/adamw_mx_kernels.hip; the bools: ALLRED_ADAMW_ZERO_GRAD,
+ * ALLRED_ADAMW_MX_RCEIL).  No routing rule and no tune key; pipe_grid caps the grid like every
+ * persistent pass.  No reference counterpart.
+ * SEMANTICS: the two blocks above composed.
+ *   NOT SKIPPED (N finite or norm_sq NULL): param, exp_avg and exp_avg_sq receive exactly the p', m'
+ *   and v' that allred_plan_adamw_all_gather_shards_f32_groups stores — info, N, c and skip are the
+ *   call's, max_norm is hyper[0].max_norm, d, o1, o2, ss, beta1, beta2, eps and bias_corr2_sqrt are
+ *   group group_of[i]'s, every operation is ONE IEEE fp32 operation in the stated order, never an fma,
+ *   division and square root correctly rounded, denormals kept — and with ALLRED_ADAMW_ZERO_GRAD +0.0f
+ *   is stored over every gradient element read.
+ *   Block b of EVERY rank's element row and scale row receives exactly what
+ *   allred_plan_all_gather_shards_mxfp8 writes from a shard that holds p': per aligned 32 elements
+ *   A = the integer maximum of bits(p'_i) & 0x7fffffff; the scale byte by the floor rule, or with
+ *   ALLRED_ADAMW_MX_RCEIL by the RCEIL rule; y_i = p'_i * 2^(-X), ONE fp32 multiply; y_i rounded to
+ *   e4m3fn, IEEE round to nearest even, +-448 on saturation, the sign kept; scale byte 0xFF and 32
+ *   element bytes 0x7F when the block holds a NaN or +-Inf.  p' is rounded ONCE, from fp32: there is
+ *   no bf16 in between.
+ *   SKIPPED STEP (N non-finite): param, exp_avg and exp_avg_sq keep their bits (they are not
+ *   written), the element rows and scale rows receive the quantisation of p, and
+ *   ALLRED_ADAMW_ZERO_GRAD still zeroes.
+ *   Everything else keeps its bits: stride skew, gaps, guards, memory past a row.
+ * GUARANTEE (tests/test_gpu_adamw_mx.py): for every bucket the four planes are bit for bit those of
+ * allred_plan_adamw_all_gather_shards_f32_groups on the same inputs, and the element rows and scale
+ * rows are bit for bit those of allred_plan_all_gather_shards_mxfp8 (same scale rule) run on the
+ * param plane that call leaves.
+ * CHECKS, all before any HIP call (a refused call writes nothing).  ALLRED_ERR_ARG: a flag bit other
+ * than ALLRED_ADAMW_ZERO_GRAD and ALLRED_ADAMW_MX_RCEIL; hyper NULL or not 16-byte aligned, norm_sq not
+ * 4-byte, info not 16-byte aligned; ngroups < 1 or > ALLRED_ADAMW_PARAM_GROUPS_MAX, a group_of[i] >=
+ * ngroups; a NULL plane or one not 16-byte aligned, shard_stride < blk or % 4 != 0; a NULL rows or
+ * scales, rows not 16-byte, scales not 8-byte aligned; elems_per_rank == 0 or not a multiple of
+ * 8 total; row_stride < elems_per_rank or % 16 != 0; scale_stride < elems_per_rank / 32 or % 8 != 0;
+ * more than 2^31 - 1 tiles of 256 elements in the list; address arithmetic that would overflow.  The
+ * plan and the count as the fp32 shard calls have them.  ALLRED_ERR_UNSUPPORTED, for the WHOLE list:
+ * a bucket that is not whole tiles (total < 8 or elems_per_rank % (256 * total) != 0).  count == 0:
+ * ALLRED_OK after the pointer and ngroups checks, nothing is launched and info is NOT written.
+ * DISJOINTNESS (csrc/adamw_mx_ranges.hpp; byte-exact and block-exact, else ALLRED_ERR_ARG): per bucket
+ * the element rows are ONE interval [rows, rows + total * row_stride), the scale rows ONE interval
+ * [scales, scales + total * scale_stride), and each of the four planes `total` separate block
+ * intervals of blk floats; against those stand [hyper, + 32 ngroups), [norm_sq, + 4 total) and
+ * [info, + 16) where given.  All pairwise disjoint, within a bucket and across buckets.  Rows, scales
+ * and the three small buffers may lie in the gap of a wide shard_stride.
+ * LAUNCHES: ALLRED_ADAMW_MX_GROUP_MAX = 32 buckets each (3920 bytes of kernel arguments, below 4 KiB),
+ * in list order, whatever the groups are: allred_plan_adamw_shards_mxfp8_launches returns
+ * ceil(count / 32), or a negative status for arguments the call would refuse (it takes no hyper).
+ * The tables travel by value, so the call can be captured into a graph; hyper is rewritten by the
+ * caller between replays. */
+#define ALLRED_ADAMW_MX_GROUP_MAX 32     /* buckets one launch of this call covers */
+#define ALLRED_ADAMW_MX_RCEIL 2          /* flags bit 1; bit 0 stays ALLRED_ADAMW_ZERO_GRAD */
+typedef struct {                        /* 80 bytes */
+    uint8_t*  rows;                     /* as allred_mx_bucket_f32: e4m3fn bytes, WRITTEN */
+    uint64_t  row_stride;               /* bytes; >= elems_per_rank, % 16 == 0 */
+    uint8_t*  scales;                   /* as allred_mx_bucket_f32: E8M0 bytes, WRITTEN */
+    uint64_t  scale_stride;             /* bytes; >= elems_per_rank / 32, % 8 == 0 */
+    uint64_t  elems_per_rank;
+    float*    param;                    /* as allred_adamw_bucket_f32: block b at plane + b * shard_stride */
+    float*    grad;
+    float*    exp_avg;
+    float*    exp_avg_sq;
+    uint64_t  shard_stride;             /* floats, ONE stride for the four planes; >= blk, % 4 == 0 */
+} allred_adamw_mx_bucket_f32;
+int allred_plan_adamw_all_gather_shards_mxfp8(
+    allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, void* stream);
+int allred_plan_adamw_shards_mxfp8_launches(const allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -499,6 +499,46 @@ class Plan:
             raise AllredError(st, "plan_all_gather_shards_mxfp8_launches")
         return st
 
+    @staticmethod
+    def _adamw_mx_buckets_f32(buckets):
+        """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, elems_per_rank, param_ptr, grad_ptr,
+        exp_avg_ptr, exp_avg_sq_ptr, shard_stride) — e4m3 element rows and E8M0 scale rows with strides in
+        bytes, four fp32 planes at one stride in floats — as an allred_adamw_mx_bucket_f32 array (None when empty)"""
+        items = [(int(rows) if rows else None, int(rs), int(scales) if scales else None, int(ss), int(n))
+                 + tuple(int(x) if x else None for x in planes) + (int(shard_stride),)
+                 for rows, rs, scales, ss, n, *planes, shard_stride in buckets]
+        return ((_lib.AdamwMxBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def adamw_all_gather_shards_mxfp8(self, buckets, group_of, hyper_ptr, ngroups: int, norm_sq_ptr=None, info_ptr=None,
+                                      zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp8: adamw_all_gather_shards_f32_groups' update of the four
+        planes, with the new parameters quantised once, from fp32, to OCP MXFP8 into every rank's element
+        row and scale row as all_gather_shards_mxfp8 writes them — one launch per ALLRED_ADAMW_MX_GROUP_MAX
+        buckets.  group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr and zero_grad: as the groups call
+        (ngroups = 1 with group_of = None: one set); rceil: the scale exponent rounded up."""
+        arr, count = self._adamw_mx_buckets_f32(buckets)
+        groups = None
+        if group_of is not None:
+            if len(group_of) != count:
+                raise ValueError(f"{len(group_of)} group indices for {count} buckets")
+            if any(not 0 <= int(g) <= 255 for g in group_of):
+                raise ValueError("a group index is one byte")
+            groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
+        flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
+        check(lib.allred_plan_adamw_all_gather_shards_mxfp8(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups),
+                                                            int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None,
+                                                            flags, _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_mxfp8")
+
+    def adamw_shards_mxfp8_launches(self, buckets) -> int:
+        """Kernel launches adamw_all_gather_shards_mxfp8 would enqueue for the list: one per
+        ALLRED_ADAMW_MX_GROUP_MAX buckets, whatever the groups."""
+        arr, count = self._adamw_mx_buckets_f32(buckets)
+        st = lib.allred_plan_adamw_shards_mxfp8_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_adamw_shards_mxfp8_launches")
+        return st
+
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
         st = np.ascontiguousarray(stamps, dtype=np.uint64)

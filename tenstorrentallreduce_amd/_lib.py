@@ -172,6 +172,17 @@ MX_GROUP_MAX = 32     # ALLRED_MX_GROUP_MAX: buckets one launch of allred_plan_a
 MX_SCALE_RCEIL = 1    # ALLRED_MX_SCALE_RCEIL: its flags bit 0
 
 
+class AdamwMxBucketF32(C.Structure):   # allred_adamw_mx_bucket_f32: MxBucketF32's rows and scales, AdamwBucketF32's four planes
+    _fields_ = [("rows", C.c_void_p), ("row_stride", C.c_uint64), ("scales", C.c_void_p), ("scale_stride", C.c_uint64),
+                ("elems_per_rank", C.c_uint64),
+                ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("shard_stride", C.c_uint64)]
+
+
+ADAMW_MX_GROUP_MAX = 32   # ALLRED_ADAMW_MX_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_mxfp8 covers
+ADAMW_MX_RCEIL = 2        # ALLRED_ADAMW_MX_RCEIL: its flags bit 1 (bit 0: ADAMW_ZERO_GRAD)
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -233,6 +244,9 @@ SIGNATURES = [
      [_P, C.POINTER(AdamwBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
+     [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -32,6 +32,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "adamw_mx_ranges.hpp"
 #include "adamw_ranges.hpp"
 #include "mx_ranges.hpp"
 #include "shard_f32_norm_ranges.hpp"
@@ -1049,6 +1050,33 @@ int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int coun
     }
 }
 
+// The checks of allred_plan_adamw_all_gather_shards_mxfp8, all before any HIP call: the flags and
+// hyper, norm_sq and info — there where required, aligned —; the plan and the count as
+// shards_f32_check has them; then adamw_mx_ranges.hpp's rules for the list: rows and scales as
+// mx_list_verdict has them, the planes as adamw_list_verdict, the tile cap, the disjointness of
+// element rows, scale rows, plane blocks and the three small intervals (which also refuses address
+// arithmetic that would overflow), and the one kernel form's shape.  dry (the launch count's query):
+// there is no hyper to check.  hyper_bytes: 32 ngroups.
+int adamw_mx_check(const allred_plan* p, const allred_adamw_mx_bucket_f32* buckets, int count, const allred_adamw_hyper* hyper,
+                   const float* norm_sq, const float* info, int flags, bool dry = false,
+                   uint64_t hyper_bytes = kAdamwHyperBytes) {
+    if (!adamw_mx_pointers_ok(hyper, norm_sq, info, flags, dry)) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count > 0 && !buckets) return ALLRED_ERR_ARG;
+    std::vector<AdamwMxRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_adamw_mx_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = AdamwMxRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.elems_per_rank,
+                                         {b.param, b.grad, b.exp_avg, b.exp_avg_sq}, b.shard_stride};
+    }
+    switch (adamw_mx_list_verdict(ranges.data(), count, (uint64_t)p->total, hyper, norm_sq, info, hyper_bytes)) {
+        case kAdamwMxOk: return ALLRED_OK;
+        case kAdamwMxUnsupported: return ALLRED_ERR_UNSUPPORTED;
+        default: return ALLRED_ERR_ARG;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1143,6 +1171,29 @@ int allred_plan_adamw_shards_f32_launches(const allred_plan* p, const allred_ada
     if (st != ALLRED_OK || count == 0) return st;
     return launch_adamw_group_f32(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/0, nullptr, nullptr, false, /*dry=*/true,
                                   nullptr);
+}
+
+// The group rules first, then adamw_mx_check with the whole hyper array as hyper's interval; all of it
+// before any HIP call.
+int allred_plan_adamw_all_gather_shards_mxfp8(allred_plan* p, const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of,
+                                              int count, const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq,
+                                              float* info, int flags, void* stream) {
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_mx_check(p, buckets, count, hyper, norm_sq, info, flags, /*dry=*/false,
+                                  kAdamwHyperBytes * (uint64_t)ngroups);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_mxfp8(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                    (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0, /*dry=*/false,
+                                    stream);
+}
+
+int allred_plan_adamw_shards_mxfp8_launches(const allred_plan* p, const allred_adamw_mx_bucket_f32* buckets, int count) {
+    const int st = adamw_mx_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_adamw_group_mxfp8(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
+                                    /*dry=*/true, nullptr);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -126,6 +126,12 @@ int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, const uint8_t
 // (mx_kernels.hip): the shard quantised to MXFP8 into every rank's rows — k_ag_group_mxfp8 —,
 // ALLRED_MX_GROUP_MAX buckets per launch.  rceil: ALLRED_MX_SCALE_RCEIL.  dry: as above.
 int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+// a list of (checked) whole-tile buckets with their four fp32 planes, element rows and scale rows
+// (adamw_mx_kernels.hip): launch_adamw_group_f32's update with ngroups >= 1 parameter groups, p' quantised
+// to MXFP8 into every rank's rows — k_adamw_ag_mxfp8 —, ALLRED_ADAMW_MX_GROUP_MAX buckets per launch.  dry: as above.
+int launch_adamw_group_mxfp8(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                             const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                             bool rceil, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
