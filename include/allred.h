@@ -55,6 +55,9 @@ extern "C" {
  * Still ABI 7: allred_adamw_mx_bucket_f32, ALLRED_ADAMW_MX_GROUP_MAX, ALLRED_ADAMW_MX_RCEIL and
  * allred_plan_adamw_all_gather_shards_mxfp8 / allred_plan_adamw_shards_mxfp8_launches are additions — the
  * AdamW step with parameter groups inside the MXFP8 all-gather's launch: p' quantised where it is computed.
+ * Still ABI 7: allred_mx2d_bucket_f32, ALLRED_MX2D_GROUP_MAX and allred_plan_all_gather_shards_mxfp8_2d /
+ * allred_plan_all_gather_shards_mxfp8_2d_launches are additions — the MXFP8 all-gather that also writes the
+ * column-wise rows (W^T with MX blocks along the rows of W), both from one read of the fp32 shard.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -712,6 +715,69 @@ typedef struct {                        /* 56 bytes */
 int allred_plan_all_gather_shards_mxfp8(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
                                         void* stream);
 int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
+/* BOTH MXFP8 ORIENTATIONS FROM ONE PASS: allred_plan_all_gather_shards_mxfp8 for a weight that is used in
+ * two GEMMs.  An MX block runs along the contraction dimension: Y = X W^T contracts over `in`, the columns
+ * of W[out][in], and takes the rows above; the input-gradient GEMM dX = dY W contracts over `out` and
+ * takes W quantised in blocks of 32 consecutive ROWS at a fixed column.  The row-wise bytes cannot serve
+ * it (their scales belong to other groups of 32 elements), so a second copy must be rounded from the
+ * fp32 master.  This call writes it in the launch that gathers the first, as W^T in the same plain
+ * linear MX row format: what is said above of the rows and v_mfma_scale_f32_16x16x128_f8f6f4 holds for
+ * the t rows as they lie, for the matrix W^T.  The AdamW step inside this launch is NOT built.
+ * Accepted plans are those of allred_plan_all_gather_shards_mxfp8; the plan supplies P only.  The kernel
+ * traces as k_ag_group_mxfp8_2d<P, false|true, false|true> (csrc/mx2d_kernels.hip; the bools:
+ * ALLRED_MX_SCALE_RCEIL, a bucket of the launch has rows).  No reference counterpart.
+ * SEMANTICS.  Every output bit is a function of the input bits.  A bucket is ONE row-major fp32 matrix
+ * W[nrows][cols], nrows = elems_per_rank / cols: float i * cols + j of the bucket is W[i][j].  The
+ * bucket is partitioned into `total` blocks of blk = elems_per_rank / total floats exactly as the other
+ * shard calls partition it — block b at shard + b * shard_stride —, so R = nrows / total rows form a block.
+ *   ROW-WISE, when rows != NULL: rows and scales receive exactly what allred_plan_all_gather_shards_mxfp8
+ *   writes for the same shard and flag.
+ *   COLUMN-WISE, always: for every column j and every aligned group of 32 rows 32 g .. 32 g + 31 take
+ *   x_k = W[32 g + k][j] and apply to x_0 .. x_31 the rule stated above for 32 consecutive floats — the
+ *   integer amax A, the NaN / Inf block, the floor or RCEIL exponent, ONE fp32 multiply, saturating RNE to
+ *   e4m3fn.  The 32 element bytes go to bytes j * nrows + 32 g + k of EVERY rank's t row, the scale byte to
+ *   byte j * (nrows / 32) + g of EVERY rank's t scale row.
+ * A t row is therefore the linear MX row of W^T[cols][nrows]: byte k of a t scale row belongs to bytes
+ * 32 k .. 32 k + 31 of the t element row.  Per rank only elems_per_rank bytes of t_rows (and of rows) and
+ * elems_per_rank / 32 bytes of t_scales (and of scales) are written; every other byte keeps its bits.  The
+ * shard is only read.
+ * CHECKS, all before any HIP call (a refused call writes nothing).  The rules of
+ * allred_plan_all_gather_shards_mxfp8 apply to rows / scales when they are given, and the same alignment
+ * and stride rules to t_rows / t_scales (16 / 8 bytes; strides >= the written extent, % 16 / % 8).
+ * ALLRED_ERR_ARG: exactly one of rows and scales NULL; t_rows, t_scales or shard NULL; cols == 0;
+ * elems_per_rank % cols != 0; address arithmetic that would overflow; a flag bit other than
+ * ALLRED_MX_SCALE_RCEIL; more than 2^31 - 1 squares of 1024 elements in the list (the launch's work
+ * items are patches of whole squares).  ALLRED_ERR_UNSUPPORTED, for the WHOLE list, the MX necessities
+ * only: total < 8, cols % 32 != 0, nrows % (32 * total) != 0 — a column block of 32 rows never straddles a
+ * shard block and a row block never straddles a row.  count == 0: ALLRED_OK, nothing launched.
+ * DISJOINTNESS (csrc/mx2d_ranges.hpp; byte-exact and block-exact, else ALLRED_ERR_ARG): per bucket up to
+ * four output intervals — [rows, + total * row_stride), [scales, + total * scale_stride),
+ * [t_rows, + total * t_row_stride), [t_scales, + total * t_scale_stride) — and the `total` shard block
+ * intervals of blk floats; all pairwise disjoint, within a bucket and across buckets.  Outputs may sit
+ * in the gap of a wide shard_stride.
+ * LAUNCHES: ONE launch covers ALLRED_MX2D_GROUP_MAX = 21 buckets (96 bytes of table per bucket: 4080
+ * bytes of kernel arguments, below 4 KiB), in list order: allred_plan_all_gather_shards_mxfp8_2d_launches
+ * returns ceil(count / 21), or a negative status for arguments the call would refuse.  The tables travel
+ * by value, so the call can be captured into a graph.  One kernel form, no routing rule and no tune key;
+ * pipe_grid caps the grid like every persistent pass. */
+#define ALLRED_MX2D_GROUP_MAX 21        /* buckets one launch covers */
+typedef struct {                        /* 96 bytes */
+    uint8_t*  rows;                     /* as allred_mx_bucket_f32; rows and scales may BOTH be NULL: column-wise only */
+    uint64_t  row_stride;
+    uint8_t*  scales;
+    uint64_t  scale_stride;
+    uint8_t*  t_rows;                   /* e4m3fn bytes of W^T, rank r's at t_rows + r * t_row_stride, WRITTEN */
+    uint64_t  t_row_stride;             /* bytes; >= elems_per_rank, % 16 == 0 */
+    uint8_t*  t_scales;                 /* E8M0 bytes of W^T, rank r's at t_scales + r * t_scale_stride, WRITTEN */
+    uint64_t  t_scale_stride;           /* bytes; >= elems_per_rank / 32, % 8 == 0 */
+    uint64_t  elems_per_rank;           /* nrows * cols */
+    uint64_t  cols;                     /* the matrix's inner dimension */
+    const float* shard;                 /* as allred_mx_bucket_f32 */
+    uint64_t  shard_stride;
+} allred_mx2d_bucket_f32;
+int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count, int flags,
+                                           void* stream);
+int allred_plan_all_gather_shards_mxfp8_2d_launches(const allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count);
 /* ADAMW INSIDE THE MXFP8 ALL-GATHER: allred_plan_adamw_all_gather_shards_f32_groups with the rows of
  * allred_plan_all_gather_shards_mxfp8 — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call), as the bf16 step is.  p' is quantised

@@ -500,6 +500,33 @@ class Plan:
         return st
 
     @staticmethod
+    def _mx2d_buckets_f32(buckets):
+        """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, t_rows_ptr, t_row_stride, t_scales_ptr,
+        t_scale_stride, elems_per_rank, cols, shard_ptr, shard_stride) — allred_mx2d_bucket_f32's order; None (or 0)
+        for rows_ptr and scales_ptr selects the column-wise outputs only — as an array of them (None when empty)"""
+        items = [tuple((int(v) if v else None) if k in (0, 2, 4, 6, 10) else int(v) for k, v in enumerate(b)) for b in buckets]
+        return ((_lib.Mx2dBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def all_gather_shards_mxfp8_2d(self, buckets, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp8_2d: every bucket is ONE row-major fp32 matrix W[nrows][cols] in
+        shard blocks; every rank receives what all_gather_shards_mxfp8 writes (MX blocks along cols: the operand
+        of Y = X W^T) where rows are given, and always the column-wise copy — W^T as linear MX rows, MX blocks
+        along the rows of W: the operand of dX = dY W — both rounded once from fp32, from one read of the shard.
+        One launch per ALLRED_MX2D_GROUP_MAX buckets.  mxfp8_dequantize on the t rows gives W^T back."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        flags = _lib.MX_SCALE_RCEIL if rceil else 0
+        check(lib.allred_plan_all_gather_shards_mxfp8_2d(self._h, arr, count, flags, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp8_2d")
+
+    def shards_mxfp8_2d_launches(self, buckets) -> int:
+        """Kernel launches all_gather_shards_mxfp8_2d would enqueue for the list: one per ALLRED_MX2D_GROUP_MAX buckets."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        st = lib.allred_plan_all_gather_shards_mxfp8_2d_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_all_gather_shards_mxfp8_2d_launches")
+        return st
+
+    @staticmethod
     def _adamw_mx_buckets_f32(buckets):
         """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, elems_per_rank, param_ptr, grad_ptr,
         exp_avg_ptr, exp_avg_sq_ptr, shard_stride) — e4m3 element rows and E8M0 scale rows with strides in

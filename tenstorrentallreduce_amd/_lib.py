@@ -172,6 +172,15 @@ MX_GROUP_MAX = 32     # ALLRED_MX_GROUP_MAX: buckets one launch of allred_plan_a
 MX_SCALE_RCEIL = 1    # ALLRED_MX_SCALE_RCEIL: its flags bit 0
 
 
+class Mx2dBucketF32(C.Structure):   # allred_mx2d_bucket_f32: MxBucketF32's rows and scales (both may be NULL), the rows of W^T, the matrix
+    _fields_ = [("rows", C.c_void_p), ("row_stride", C.c_uint64), ("scales", C.c_void_p), ("scale_stride", C.c_uint64),
+                ("t_rows", C.c_void_p), ("t_row_stride", C.c_uint64), ("t_scales", C.c_void_p), ("t_scale_stride", C.c_uint64),
+                ("elems_per_rank", C.c_uint64), ("cols", C.c_uint64), ("shard", C.c_void_p), ("shard_stride", C.c_uint64)]
+
+
+MX2D_GROUP_MAX = 21   # ALLRED_MX2D_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8_2d covers
+
+
 class AdamwMxBucketF32(C.Structure):   # allred_adamw_mx_bucket_f32: MxBucketF32's rows and scales, AdamwBucketF32's four planes
     _fields_ = [("rows", C.c_void_p), ("row_stride", C.c_uint64), ("scales", C.c_void_p), ("scale_stride", C.c_uint64),
                 ("elems_per_rank", C.c_uint64),
@@ -244,6 +253,8 @@ SIGNATURES = [
      [_P, C.POINTER(AdamwBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
+    ("allred_plan_all_gather_shards_mxfp8_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),

@@ -34,6 +34,7 @@
 #include "internal.hpp"
 #include "adamw_mx_ranges.hpp"
 #include "adamw_ranges.hpp"
+#include "mx2d_ranges.hpp"
 #include "mx_ranges.hpp"
 #include "shard_f32_norm_ranges.hpp"
 #include "shard_f32_ranges.hpp"
@@ -1050,6 +1051,29 @@ int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int coun
     }
 }
 
+// The checks of allred_plan_all_gather_shards_mxfp8_2d, all before any HIP call: mx_check's with
+// mx2d_ranges.hpp's rules for the list — the row-wise outputs optional, the t outputs, the matrix
+// shape, the cap on the work items, the disjointness of up to four output intervals and the shard
+// blocks (which also refuses address arithmetic that would overflow), then the MX necessities.
+int mx2d_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags) {
+    if (!mx2d_flags_ok(flags)) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count == 0) return ALLRED_OK;
+    if (!buckets) return ALLRED_ERR_ARG;
+    std::vector<Mx2dRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_mx2d_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = Mx2dRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.t_rows, b.t_row_stride, b.t_scales,
+                                      b.t_scale_stride, b.elems_per_rank, b.cols, b.shard, b.shard_stride};
+    }
+    switch (mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total)) {
+        case kMx2dOk: return ALLRED_OK;
+        case kMx2dUnsupported: return ALLRED_ERR_UNSUPPORTED;
+        default: return ALLRED_ERR_ARG;
+    }
+}
+
 // The checks of allred_plan_adamw_all_gather_shards_mxfp8, all before any HIP call: the flags and
 // hyper, norm_sq and info — there where required, aligned —; the plan and the count as
 // shards_f32_check has them; then adamw_mx_ranges.hpp's rules for the list: rows and scales as
@@ -1094,6 +1118,21 @@ int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* p, const all
     const int st = mx_check(p, buckets, count, 0);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_ag_group_mxfp8(buckets, count, p->total, false, /*dry=*/true, nullptr);
+}
+
+int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,
+                                           void* stream) {
+    const int st = mx2d_check(p, buckets, count, flags);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp8_2d(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, /*dry=*/false, stream);
+}
+
+int allred_plan_all_gather_shards_mxfp8_2d_launches(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count) {
+    const int st = mx2d_check(p, buckets, count, 0);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_ag_group_mxfp8_2d(buckets, count, p->total, false, /*dry=*/true, nullptr);
 }
 
 int allred_plan_reduce_scatter_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {

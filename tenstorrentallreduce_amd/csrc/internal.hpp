@@ -126,6 +126,10 @@ int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, const uint8_t
 // (mx_kernels.hip): the shard quantised to MXFP8 into every rank's rows — k_ag_group_mxfp8 —,
 // ALLRED_MX_GROUP_MAX buckets per launch.  rceil: ALLRED_MX_SCALE_RCEIL.  dry: as above.
 int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+// a list of (checked) buckets of one fp32 matrix each (mx2d_kernels.hip): the shard quantised to MXFP8
+// both row-wise (where a bucket has rows) and column-wise, as W^T, into every rank's rows —
+// k_ag_group_mxfp8_2d —, ALLRED_MX2D_GROUP_MAX buckets per launch.  rceil, dry: as above.
+int launch_ag_group_mxfp8_2d(const allred_mx2d_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
 // a list of (checked) whole-tile buckets with their four fp32 planes, element rows and scale rows
 // (adamw_mx_kernels.hip): launch_adamw_group_f32's update with ngroups >= 1 parameter groups, p' quantised
 // to MXFP8 into every rank's rows — k_adamw_ag_mxfp8 —, ALLRED_ADAMW_MX_GROUP_MAX buckets per launch.  dry: as above.
