@@ -8,11 +8,14 @@ holds W^T.  Everything BIT FOR BIT, whole buffers, around sentinel skews and gua
 test_gpu_shards_f32's (compact / wide / flat).  The data is mx2d_ref.hard_t (the 24 planted blocks down the
 columns) and mx2d_ref.hard_rows (along the rows)."""
 import functools
+import os
+import re
 
 import numpy as np
 import pytest
 
 import far_arena
+import mx2d_cases as mc
 import mx2d_ref
 import mxfp8_ref as ref
 import tenstorrentallreduce_amd as t
@@ -28,10 +31,12 @@ SENT8 = mxt.SENT8
 Shards, sched, grids, layouts, any_plan, stream, to_dev8 = (mxt.Shards, mxt.sched, mxt.grids, mxt.layouts, mxt.any_plan,
                                                             mxt.stream, mxt.to_dev8)
 G = _lib.MX2D_GROUP_MAX
-# (cols, R): one square per block; a column count that is no power of two with two row groups; non-square;
-# a whole 64 x 64 patch; two column groups of one row group
-SHAPES = ((32, 32), (96, 64), (160, 32), (64, 64), (128, 32))
+# (cols, R), tests/mx2d_cases.py: one square per block; three column groups of a patch two squares high; five column
+# groups; a whole 64 x 64 patch; two column groups.  ONE row group per block, every one (tests/test_mx2d_classes.py)
+SHAPES = mc.SHAPES
 KINDS = ("hard_t", "hard_rows")
+with open(os.path.join(os.path.dirname(os.path.abspath(t.__file__)), "csrc", "mx2d_span.hpp")) as _f:
+    LG_SIDE = int(re.search(r"#define TSA_MX2D_LG_SIDE (\d+)", _f.read()).group(1))
 
 
 def tf(x):
@@ -44,7 +49,12 @@ def kernel(total, rceil, rows=True):
 
 def shapes_of(total):
     """the bucket list of a schedule: P = 64 runs one square per block"""
-    return ((32, 32), (32, 32), (32, 32)) if total == 64 else SHAPES
+    return mc.SHAPES_64 if total == 64 else SHAPES
+
+
+def row_group_shapes(total):
+    """the bucket list of the tests of several row groups per shard block"""
+    return mc.ROW_GROUP_SHAPES_64 if total == 64 else mc.ROW_GROUP_SHAPES
 
 
 @functools.lru_cache(maxsize=None)
@@ -142,7 +152,11 @@ def test_both_orientations_in_every_rank(algo, side, total, layout, grid):
 def test_rows_and_t_rows_are_what_the_row_wise_call_writes(algo, side, total, rceil):
     """rows / scales: all_gather_shards_mxfp8 on the same shard.  t rows / t scales: all_gather_shards_mxfp8 on a
     shard buffer that holds W^T.  Then rows = scales = None: ROWS = false in the trace, the t outputs identical."""
-    buckets, keys = make(total, shapes_of(total), seed=1)
+    held_against_the_row_wise_call(algo, side, total, rceil, shapes_of(total), seed=1)
+
+
+def held_against_the_row_wise_call(algo, side, total, rceil, shapes, seed):
+    buckets, keys = make(total, shapes, seed=seed)
     shards = Shards(buckets, "wide")
     fill(shards, "hard_t", keys)
     plan = any_plan(algo, side, total)
@@ -164,7 +178,7 @@ def test_rows_and_t_rows_are_what_the_row_wise_call_writes(algo, side, total, rc
             for name, x, y in zip(("t rows", "t scales"), g[1], b.got()):
                 assert np.array_equal(x, y), f"bucket {i}: {name} differ from all_gather_shards_mxfp8 on a shard holding W^T"
         # column-wise only
-        only, _ = make(total, shapes_of(total), rows=False, seed=1)
+        only, _ = make(total, shapes, rows=False, seed=seed)
         s3 = Shards(only, "wide")
         fill(s3, "hard_t", keys)
         with t.launch_trace() as tr:
@@ -462,6 +476,131 @@ def test_t_rows_feed_the_scaled_mfma():
     want = ref.dequantize64(want4[2], want4[3]).reshape(cols, k)
     nan_rows = np.isnan(want).any(axis=1)
     assert nan_rows.any() and not nan_rows.all()
+    for r in (0, total - 1):
+        for half in (0, 1):
+            rows = slice(16 * half, 16 * half + 16)
+            got = mfma.every_element(b.c.buf[0].data_ptr() + r * b.c.row_stride + 16 * half * k, k,
+                                     b.c.buf[1].data_ptr() + r * b.c.scale_stride + 16 * half * (k // 32), k // 32, 16, k)
+            nr = nan_rows[rows]
+            assert np.isnan(got[nr]).all() and not np.isnan(got[~nr]).any()
+            mfma.report(f"rank {r} rows {rows}", mfma.same_value(got[~nr], want[rows][~nr], f"rank {r}'s t row"))
+    plan.close()
+
+
+# ------------------------------------------------------------------ 8. several row groups per shard block
+# SHAPES above has ONE row group per block at the build's 64 x 64 patch: the row-group terms of mx2d_unit_at — in the
+# shard read, in the row-wise rows, in the t rows — vanish there.  mc.ROW_GROUP_SHAPES has two or three row groups
+# under each patch class; tests/test_mx2d_classes.py shows on the CPU which mistakes only these shapes see.
+ROW_GROUP_SEED = 4
+
+
+def squares_by_workgroup(total, shapes, grid):
+    """per workgroup, the square counts of the units it walks: unit x of the launch — the buckets in list order, a
+    bucket's blocks in order, a block's units in order (group_span.hpp) — goes to workgroup x % grid"""
+    squares = []
+    for cols, R in shapes:
+        lgh, lgw, rgs, cgs = mc.shape_class(cols, R, LG_SIDE)
+        squares += [1 << (lgh + lgw)] * (total * rgs * cgs)
+    return [squares[g::grid] for g in range(grid)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@grids
+@layouts
+@sched
+def test_several_row_groups_per_block(algo, side, total, layout, grid, kind):
+    shapes = row_group_shapes(total)
+    assert all(mc.shape_class(cols, R, LG_SIDE)[2] >= 2 for cols, R in shapes)
+    if grid:   # every workgroup walks patches of one, two and four squares: the LDS images rotate across unequal patches
+        walks = squares_by_workgroup(total, shapes, grid)
+        assert len(walks) == grid and all(set(w) == {1, 2, 4} and len(w) >= 3 for w in walks), [sorted(set(w)) for w in walks]
+    buckets, keys = make(total, shapes, seed=ROW_GROUP_SEED)
+    shards = Shards(buckets, layout)
+    fill(shards, kind, keys)
+    plan = any_plan(algo, side, total)
+    with t.tuned(pipe_grid=grid):
+        assert plan.shards_mxfp8_2d_launches(shards.args()) == 1
+        for rceil in (False, True):
+            for b in buckets:
+                b.restore()
+            with t.launch_trace() as tr:
+                plan.all_gather_shards_mxfp8_2d(shards.args(), rceil=rceil, stream=stream())
+            assert tr.kernels == [kernel(total, rceil)]
+            if grid:
+                assert tr.grids == [grid]
+            check_all(buckets, kind, keys, rceil, "rows = mxfp8(W), t rows = mxfp8(W^T), several row groups per block")
+            shards_unchanged(shards)
+    plan.close()
+
+
+@pytest.mark.parametrize("rceil", [False, True])
+@pytest.mark.parametrize("side,total", [(4, 8), (4, 16), (8, 64)])
+def test_row_groups_rows_and_t_rows_are_what_the_row_wise_call_writes(side, total, rceil):
+    """test 2's guarantees, GPU against GPU, on the lists of several row groups per block"""
+    held_against_the_row_wise_call(t.SWING, side, total, rceil, row_group_shapes(total), seed=ROW_GROUP_SEED)
+
+
+@pytest.mark.parametrize("rows_first", [True, False], ids=["rows-then-none", "none-then-rows"])
+def test_a_launch_with_rows_beside_a_launch_without(rows_first):
+    """G + 2 buckets, two launches: the buckets of one have row-wise outputs (but for every fourth), those of the other
+    have none.  The launcher's side table is reset between the launches: the trace says ROWS = true for the one and
+    ROWS = false for the other, in either order.  Each launch holds buckets of several row groups per block."""
+    algo, side, total = t.SWING, 4, 8
+    cycle = ((32, 96), (96, 64), (64, 128))
+    shapes = [cycle[i % 3] for i in range(G + 2)]
+    for launch in (shapes[:G], shapes[G:]):
+        assert any(mc.shape_class(cols, R, LG_SIDE)[2] >= 2 for cols, R in launch)
+    has_rows = [(i < G) == rows_first and i % 4 != 3 for i in range(G + 2)]
+    assert any(has_rows[:G]) == rows_first and any(has_rows[G:]) != rows_first
+    buckets = [Bucket2d(total, cols, R, skew=i % 3 == 0, rows=has_rows[i]) for i, (cols, R) in enumerate(shapes)]
+    keys = [(total, cols, R, 100 + i % 5) for i, (cols, R) in enumerate(shapes)]
+    shards = Shards(buckets, "flat")
+    fill(shards, "hard_t", keys)
+    plan = any_plan(algo, side, total)
+    assert plan.shards_mxfp8_2d_launches(shards.args()) == 2
+    with t.launch_trace() as tr:
+        plan.all_gather_shards_mxfp8_2d(shards.args(), rceil=True, stream=stream())
+    assert tr.kernels == [kernel(total, True, rows=rows_first), kernel(total, True, rows=not rows_first)]
+    check_all(buckets, "hard_t", keys, True, f"{G} buckets {'with' if rows_first else 'without'} rows, then 2 {'without' if rows_first else 'with'}")
+    shards_unchanged(shards)
+    plan.close()
+
+
+def finite_in_the_odd_columns(W):
+    """W = hard_t with nrows = 768: a column is 24 MX blocks, every planted kind once, so every t row would hold a NaN
+    block and the MFMA would answer NaN for every matrix row.  In the odd columns each block with a NaN or an Inf is
+    replaced by the block eight above it, a finite kind: sixteen matrix rows keep their NaNs, sixteen are finite."""
+    import test_gpu_mx_consumer as mfma
+    nrows, cols = W.shape
+    wt = np.ascontiguousarray(W.T).reshape(cols, nrows // 32, 32)
+    kind = mx2d_ref.planted_kind(nrows, cols)
+    for j in range(1, cols, 2):
+        for b in np.flatnonzero(np.isin(kind[j], mfma.NAN_BLOCKS)):
+            assert b >= 8 and kind[j, b - 8] not in mfma.NAN_BLOCKS
+            wt[j, b] = wt[j, b - 8]
+    assert np.isfinite(wt[1::2]).all() and not np.isfinite(wt[0::2]).all(axis=(1, 2)).any()
+    return np.ascontiguousarray(wt.reshape(cols, nrows).T)
+
+
+def test_t_rows_across_row_groups_feed_the_scaled_mfma():
+    """8 ranks, one bucket of cols = 32, R = 96: a t row is W^T, 32 matrix rows of k = 768 bytes, six k-steps, and each
+    matrix row crosses three row groups in every shard block — the neighbours along nrows that the test above never
+    crosses inside a block.  Rank 0's and the last rank's t rows go to the MFMA as they lie, 16 matrix rows at a time."""
+    import test_gpu_mx_consumer as mfma
+    algo, side, total, cols, R = t.SWING, 4, 8, 32, 96
+    assert mc.shape_class(cols, R, LG_SIDE)[2] == 3
+    k = total * R
+    W = finite_in_the_odd_columns(matrix("hard_t", total, cols, R, 22))
+    b = Bucket2d(total, cols, R, skew=True)
+    shards = Shards([b], "flat")
+    shards.fill([mx2d_ref.blocks(W, total)])
+    plan = any_plan(algo, side, total)
+    plan.all_gather_shards_mxfp8_2d(shards.args(), stream=stream())
+    want4 = mx2d_ref.expected_rows(W, total) + mx2d_ref.expected_t(W)
+    b.check(want4, "the rows the MFMA is about to read")
+    want = ref.dequantize64(want4[2], want4[3]).reshape(cols, k)
+    nan_rows = np.isnan(want).any(axis=1)
+    assert np.array_equal(nan_rows, np.arange(cols) % 2 == 0)
     for r in (0, total - 1):
         for half in (0, 1):
             rows = slice(16 * half, 16 * half + 16)

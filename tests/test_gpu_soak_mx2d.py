@@ -1,11 +1,11 @@
 """k_ag_group_mxfp8_2d through the replay soak (tests/soak.py), as tests/test_gpu_soak_adamw_mx.py soaks
 k_adamw_ag_mxfp8: every instantiated rank count and all four (RCEIL, ROWS) values (tests/mx2d_cases.py,
-SOAK_CASES; tests/test_mx2d_table.py holds the table against the kernel file), on an unequal list of four
-matrices in the flat layout at pipe_grid 5 — every workgroup walks at least three work units, so the LDS
-image rotates — under `idle`, `uniform` and `uneven` load.
+SOAK_CASES; tests/test_mx2d_table.py holds the table against the kernel file), on an unequal list of six
+matrices, two of them of several row groups per shard block, in the flat layout at pipe_grid 5 — every
+workgroup walks at least three work units, so the LDS image rotates — under `idle`, `uniform` and `uneven` load.
 
 One capture, soak.R replays back to back, two datasets (soak_cases.finite_floats on two seeds) alternating in
-the same buffers; every buffer — the four row sets with skew and guard row, the flat shard buffer with its
+the same buffers; every buffer — each bucket's four row sets with skew and guard row, the flat shard buffer with its
 guard — restored before and compared whole after every replay, on the device."""
 import numpy as np
 import pytest

@@ -6,11 +6,17 @@ offsets mx2d_unit_at gives — shard, row-wise bytes, row-wise scales, t bytes, 
 the patches in order (block, row group, column group) computed in 128 bits from the matrix coordinates.  At the
 four small shapes (P, cols, R) = (8, 32, 32), (8, 96, 64), (64, 32, 32), (16, 160, 32), and at (8, 64, 64) and
 (8, 128, 32) where the patch is wider than a square, every byte the patches cover is counted: every element byte,
-every scale byte of both orientations and every shard float exactly once, none outside.  One shape has cols * nrows
-and r * t_row_stride beyond 2^32: its units are sampled."""
+every scale byte of both orientations and every shard float exactly once, none outside.  The same count is taken
+at every (P, cols, R) a GPU test runs (tests/mx2d_cases.py), the shapes of several row groups per shard block among
+them, and what the header makes of each shape — lgh, lgw, cgs, units — is printed and compared with
+mx2d_cases.shape_class, the restatement the census of tests/test_mx2d_classes.py rests on.  One shape has
+cols * nrows and r * t_row_stride beyond 2^32: its units are sampled."""
 import os
+import re
 import shutil
 import subprocess
+
+import mx2d_cases as mc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tenstorrentallreduce_amd", "csrc")
@@ -63,6 +69,8 @@ static void small(uint64_t P, uint64_t cols, uint64_t R, uint64_t gap) {
     const uint64_t H = 32ull << s.lgh, Wd = 32ull << s.lgw;
     if (cols % Wd || R % H || units != (cols / Wd) * (R / H) || all != units * P || s.cgs != cols / Wd)
         fail("shape", cols, nrows, 0, 0, units, (cols / Wd) * (R / H));
+    std::printf("shape %llu %llu %llu: %u %u %u %llu\n", (unsigned long long)P, (unsigned long long)cols, (unsigned long long)R, s.lgh,
+                s.lgw, s.cgs, (unsigned long long)units);
     if ((int)s.lgh > tsa::kMx2dLgSide || (int)s.lgw > tsa::kMx2dLgSide) fail("side", cols, nrows, 0, 0, s.lgh, s.lgw);
     // the widest patch the divisibility allows, up to the cap
     if ((int)s.lgw < tsa::kMx2dLgSide && (cols / Wd) % 2 == 0) fail("lgw", cols, nrows, 0, 0, s.lgw, 0);
@@ -99,6 +107,8 @@ int main() {
     small(8, 64, 64, 0);
     small(8, 128, 32, 8);
     small(8, 256, 128, 0);
+    // every (P, cols, R) of the GPU tests' lists (tests/mx2d_cases.py), several row groups per block among them
+@TABLE@
     // cols * nrows = 2^33 + ..., the last rank's t row beyond 2^32 bytes
     {
         const uint64_t P = 8, cols = 96 * 1024 + 32, R = 1u << 14, nrows = P * R, stride = R * cols + 4096;
@@ -134,11 +144,23 @@ int main() {
 """
 
 
+LITERAL = ((8, 32, 32), (8, 96, 64), (64, 32, 32), (16, 160, 32), (8, 64, 64), (8, 128, 32), (8, 256, 128))   # main's own small() calls
+GAPS = (0, 64, 4, 8)   # floats between the shard blocks, in turn
+
+
+def table():
+    """(P, cols, R) of every shape a GPU test runs, each once: the shape tests' lists at their rank counts, the soak's at all"""
+    lists = [((p,), mc.gpu_shapes(p)) for p in mc.SOAK_RANKS] + [(mc.SOAK_RANKS, mc.SOAK_SHAPES)]
+    return list(dict.fromkeys((p, cols, R) for ranks, shapes in lists for p in ranks for cols, R in shapes))
+
+
 def test_mx2d_span_matches_brute_force(tmp_path):
     gxx = shutil.which("g++")
     assert gxx, "g++ is needed to compile the mx2d_span check"
     src = tmp_path / "mx2d_span_check.cpp"
-    src.write_text(PROGRAM)
+    calls = [f"    small({p}, {cols}, {R}, {GAPS[i % 4]});" for i, (p, cols, R) in enumerate(table())]
+    assert all((p, *s) in table() for p in mc.GPU_RANKS for s in mc.ROW_GROUP_SHAPES) and all((64, *s) in table() for s in mc.ROW_GROUP_SHAPES_64)
+    src.write_text(PROGRAM.replace("@TABLE@", "\n".join(calls)))
     exe = tmp_path / "mx2d_span_check"
     subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", CSRC, str(src),
@@ -146,3 +168,13 @@ def test_mx2d_span_matches_brute_force(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "mx2d_span ok" in run.stdout
+    # what the C++ made of every shape it walked, against mx2d_cases.shape_class
+    lg = int(re.search(r"#define TSA_MX2D_LG_SIDE (\d+)", open(os.path.join(CSRC, "mx2d_span.hpp")).read()).group(1))
+    printed = {}
+    for m in re.finditer(r"^shape (\d+) (\d+) (\d+): (\d+) (\d+) (\d+) (\d+)$", run.stdout, re.M):
+        p, cols, R, lgh, lgw, cgs, units = map(int, m.groups())
+        printed[p, cols, R] = (lgh, lgw, cgs, units)
+    assert set(printed) == set(LITERAL) | set(table()), sorted(set(printed) ^ (set(LITERAL) | set(table())))
+    for (p, cols, R), got in printed.items():
+        lgh, lgw, rgs, cgs = mc.shape_class(cols, R, lg)
+        assert got == (lgh, lgw, cgs, rgs * cgs), f"P={p} cols={cols} R={R}: the header says (lgh, lgw, cgs, units) = {got}"
