@@ -58,6 +58,9 @@ extern "C" {
  * Still ABI 7: allred_mx2d_bucket_f32, ALLRED_MX2D_GROUP_MAX and allred_plan_all_gather_shards_mxfp8_2d /
  * allred_plan_all_gather_shards_mxfp8_2d_launches are additions — the MXFP8 all-gather that also writes the
  * column-wise rows (W^T with MX blocks along the rows of W), both from one read of the fp32 shard.
+ * Still ABI 7: allred_adamw_mx2d_bucket_f32, ALLRED_ADAMW_MX2D_GROUP_MAX and
+ * allred_plan_adamw_all_gather_shards_mxfp8_2d / allred_plan_adamw_shards_mxfp8_2d_launches are additions — the
+ * AdamW step inside that launch: both orientations of p', each rounded once from fp32.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -722,7 +725,8 @@ int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const 
  * it (their scales belong to other groups of 32 elements), so a second copy must be rounded from the
  * fp32 master.  This call writes it in the launch that gathers the first, as W^T in the same plain
  * linear MX row format: what is said above of the rows and v_mfma_scale_f32_16x16x128_f8f6f4 holds for
- * the t rows as they lie, for the matrix W^T.  The AdamW step inside this launch is NOT built.
+ * the t rows as they lie, for the matrix W^T.  allred_plan_adamw_all_gather_shards_mxfp8_2d below runs
+ * the AdamW step inside this launch.
  * Accepted plans are those of allred_plan_all_gather_shards_mxfp8; the plan supplies P only.  The kernel
  * traces as k_ag_group_mxfp8_2d<P, false|true, false|true> (csrc/mx2d_kernels.hip; the bools:
  * ALLRED_MX_SCALE_RCEIL, a bucket of the launch has rows).  No reference counterpart.
@@ -853,6 +857,84 @@ int allred_plan_adamw_all_gather_shards_mxfp8(
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, void* stream);
 int allred_plan_adamw_shards_mxfp8_launches(const allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets, int count);
+/* ADAMW INSIDE THE 2D MXFP8 ALL-GATHER: the call above with the outputs of
+ * allred_plan_all_gather_shards_mxfp8_2d — the MXFP8 training step in TWO launches
+ * (allred_plan_reduce_scatter_shards_f32_norm, then this call) with BOTH GEMM operands, the row-wise rows
+ * of Y = X W^T and the column-wise rows of dX = dY W, each rounded ONCE from the fp32 p'.  No third launch
+ * and no second read of the masters.  ONE entry point and ONE kernel form, always with parameter groups:
+ * ngroups = 1 with group_of = NULL is the one-set call.  hyper, group_of, ngroups, norm_sq, info and the
+ * flags are those of allred_plan_adamw_all_gather_shards_mxfp8; the eight output fields, elems_per_rank
+ * and cols those of allred_mx2d_bucket_f32 (rows = scales = NULL: the column-wise outputs only); the four
+ * planes and shard_stride those of allred_adamw_bucket_f32: a bucket is ONE row-major matrix
+ * W[nrows][cols] held four times, block b of every plane at plane + b * shard_stride.  The kernel traces as
+ * k_adamw_ag_mxfp8_2d<P, false|true, false|true, false|true> (csrc/adamw_mx2d_kernels.hip; the bools:
+ * ALLRED_ADAMW_ZERO_GRAD, ALLRED_ADAMW_MX_RCEIL, a bucket of the launch has rows).  No routing rule and
+ * no tune key; pipe_grid caps the grid like every persistent pass.  No reference counterpart.
+ * SEMANTICS: the two blocks above composed; every output bit is a function of the input bits.
+ *   NOT SKIPPED (N finite or norm_sq NULL): param, exp_avg and exp_avg_sq receive exactly the p', m'
+ *   and v' that allred_plan_adamw_all_gather_shards_f32_groups stores — info, N, c and skip are the
+ *   call's, max_norm is hyper[0].max_norm, the other values are group group_of[i]'s, every operation is
+ *   ONE IEEE fp32 operation in the stated order, never an fma — and with ALLRED_ADAMW_ZERO_GRAD +0.0f is
+ *   stored over every gradient element read.
+ *   rows / scales (when given), t_rows and t_scales of EVERY rank receive exactly what
+ *   allred_plan_all_gather_shards_mxfp8_2d writes from a shard that holds p' (ALLRED_ADAMW_MX_RCEIL: with
+ *   ALLRED_MX_SCALE_RCEIL): row-wise the rule for 32 consecutive floats of a row, column-wise the same
+ *   rule for x_k = p'[32 g + k][j], the bytes at j * nrows + 32 g + k of the t row, the scale byte at
+ *   j * (nrows / 32) + g of the t scale row.  Both are rounded from the fp32 p', neither from the other.
+ *   SKIPPED STEP (N non-finite): param, exp_avg and exp_avg_sq keep their bits (they are not written),
+ *   all four outputs receive the quantisation of p, and ALLRED_ADAMW_ZERO_GRAD still zeroes.
+ *   Everything else keeps its bits: stride skew, gaps, guards, memory past a row.
+ * GUARANTEE (tests/test_gpu_adamw_mx2d.py): for every bucket the four planes are bit for bit those of
+ * allred_plan_adamw_all_gather_shards_f32_groups on the same inputs, and the four outputs are bit for bit
+ * those of allred_plan_all_gather_shards_mxfp8_2d (same scale rule) run on the param plane that call leaves.
+ * CHECKS, all before any HIP call (a refused call writes nothing).  ALLRED_ERR_ARG: a flag bit other
+ * than ALLRED_ADAMW_ZERO_GRAD and ALLRED_ADAMW_MX_RCEIL; hyper NULL or not 16-byte aligned, norm_sq not
+ * 4-byte, info not 16-byte aligned; ngroups < 1 or > ALLRED_ADAMW_PARAM_GROUPS_MAX, a group_of[i] >=
+ * ngroups; a NULL plane or one not 16-byte aligned, shard_stride < blk or % 4 != 0; every ALLRED_ERR_ARG
+ * rule of allred_plan_all_gather_shards_mxfp8_2d for the outputs, elems_per_rank and cols (exactly one of
+ * rows and scales NULL; t_rows or t_scales NULL; alignment 16 / 8; strides; cols == 0 or
+ * elems_per_rank % cols != 0; more than 2^31 - 1 squares of 1024 elements in the list); address
+ * arithmetic that would overflow.  The plan and the count as the fp32 shard calls have them.
+ * ALLRED_ERR_UNSUPPORTED, for the WHOLE list, the 2D call's MX necessities: total < 8, cols % 32 != 0,
+ * nrows % (32 * total) != 0.  They imply whole tiles (blk is a multiple of 1024).  count == 0: ALLRED_OK
+ * after the pointer and ngroups checks, nothing is launched and info is NOT written.
+ * DISJOINTNESS (csrc/adamw_mx2d_ranges.hpp; byte-exact and block-exact, else ALLRED_ERR_ARG): per bucket
+ * up to four output intervals — [rows, + total * row_stride), [scales, + total * scale_stride),
+ * [t_rows, + total * t_row_stride), [t_scales, + total * t_scale_stride) — and each of the four planes'
+ * `total` separate block intervals of blk floats; against those stand [hyper, + 32 ngroups),
+ * [norm_sq, + 4 total) and [info, + 16) where given.  All pairwise disjoint, within a bucket and across
+ * buckets.  Outputs and the three small buffers may lie in the gap of a wide shard_stride.
+ * LAUNCHES: ALLRED_ADAMW_MX2D_GROUP_MAX = 16 buckets each (120 bytes of table and one group byte per
+ * bucket: 4032 bytes of kernel arguments, below 4 KiB; seventeen pass it), in list order, whatever the
+ * groups are: allred_plan_adamw_shards_mxfp8_2d_launches returns ceil(count / 16), or a negative status
+ * for arguments the call would refuse (it takes no hyper).  info is written once, by the first launch.
+ * The tables travel by value, so the call can be captured into a graph; hyper is rewritten by the caller
+ * between replays. */
+#define ALLRED_ADAMW_MX2D_GROUP_MAX 16   /* buckets one launch of this call covers */
+typedef struct {                        /* 120 bytes */
+    uint8_t*  rows;                     /* as allred_mx2d_bucket_f32; rows and scales may BOTH be NULL: column-wise only */
+    uint64_t  row_stride;
+    uint8_t*  scales;
+    uint64_t  scale_stride;
+    uint8_t*  t_rows;                   /* e4m3fn bytes of p'^T, rank r's at t_rows + r * t_row_stride, WRITTEN */
+    uint64_t  t_row_stride;             /* bytes; >= elems_per_rank, % 16 == 0 */
+    uint8_t*  t_scales;                 /* E8M0 bytes of p'^T, rank r's at t_scales + r * t_scale_stride, WRITTEN */
+    uint64_t  t_scale_stride;           /* bytes; >= elems_per_rank / 32, % 8 == 0 */
+    uint64_t  elems_per_rank;           /* nrows * cols */
+    uint64_t  cols;                     /* the matrix's inner dimension */
+    float*    param;                    /* as allred_adamw_bucket_f32: block b at plane + b * shard_stride */
+    float*    grad;
+    float*    exp_avg;
+    float*    exp_avg_sq;
+    uint64_t  shard_stride;             /* floats, ONE stride for the four planes; >= blk, % 4 == 0 */
+} allred_adamw_mx2d_bucket_f32;
+int allred_plan_adamw_all_gather_shards_mxfp8_2d(
+    allred_plan* plan, const allred_adamw_mx2d_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, void* stream);
+int allred_plan_adamw_shards_mxfp8_2d_launches(const allred_plan* plan, const allred_adamw_mx2d_bucket_f32* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -566,6 +566,46 @@ class Plan:
             raise AllredError(st, "plan_adamw_shards_mxfp8_launches")
         return st
 
+    @staticmethod
+    def _adamw_mx2d_buckets_f32(buckets):
+        """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, t_rows_ptr, t_row_stride, t_scales_ptr,
+        t_scale_stride, elems_per_rank, cols, param_ptr, grad_ptr, exp_avg_ptr, exp_avg_sq_ptr, shard_stride) —
+        allred_adamw_mx2d_bucket_f32's order; None (or 0) for rows_ptr and scales_ptr selects the column-wise
+        outputs only — as an array of them (None when empty)"""
+        items = [tuple((int(v) if v else None) if k in (0, 2, 4, 6, 10, 11, 12, 13) else int(v) for k, v in enumerate(b))
+                 for b in buckets]
+        return ((_lib.AdamwMx2dBucketF32 * len(items))(*items) if items else None), len(items)
+
+    def adamw_all_gather_shards_mxfp8_2d(self, buckets, group_of, hyper_ptr, ngroups: int, norm_sq_ptr=None, info_ptr=None,
+                                         zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp8_2d: adamw_all_gather_shards_mxfp8's update of the four
+        planes of every bucket — ONE row-major matrix W[nrows][cols] in shard blocks —, with the new
+        parameters quantised once, from fp32, into BOTH orientations as all_gather_shards_mxfp8_2d writes
+        them: the row-wise rows (where given) and the column-wise rows of every rank.  One launch per
+        ALLRED_ADAMW_MX2D_GROUP_MAX buckets.  The other arguments: as adamw_all_gather_shards_mxfp8."""
+        arr, count = self._adamw_mx2d_buckets_f32(buckets)
+        groups = None
+        if group_of is not None:
+            if len(group_of) != count:
+                raise ValueError(f"{len(group_of)} group indices for {count} buckets")
+            if any(not 0 <= int(g) <= 255 for g in group_of):
+                raise ValueError("a group index is one byte")
+            groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
+        flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
+        check(lib.allred_plan_adamw_all_gather_shards_mxfp8_2d(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups),
+                                                               int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None,
+                                                               flags, _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_mxfp8_2d")
+
+    def adamw_shards_mxfp8_2d_launches(self, buckets) -> int:
+        """Kernel launches adamw_all_gather_shards_mxfp8_2d would enqueue for the list: one per
+        ALLRED_ADAMW_MX2D_GROUP_MAX buckets, whatever the groups."""
+        arr, count = self._adamw_mx2d_buckets_f32(buckets)
+        st = lib.allred_plan_adamw_shards_mxfp8_2d_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_adamw_shards_mxfp8_2d_launches")
+        return st
+
     def rank_zones(self, stamps: np.ndarray):
         """Per-rank ALL_RED_LOOP (start, end) in 100 MHz ticks from host stamps."""
         st = np.ascontiguousarray(stamps, dtype=np.uint64)

@@ -192,6 +192,17 @@ ADAMW_MX_GROUP_MAX = 32   # ALLRED_ADAMW_MX_GROUP_MAX: buckets one launch of all
 ADAMW_MX_RCEIL = 2        # ALLRED_ADAMW_MX_RCEIL: its flags bit 1 (bit 0: ADAMW_ZERO_GRAD)
 
 
+class AdamwMx2dBucketF32(C.Structure):   # allred_adamw_mx2d_bucket_f32: Mx2dBucketF32's outputs and matrix, AdamwBucketF32's four planes
+    _fields_ = [("rows", C.c_void_p), ("row_stride", C.c_uint64), ("scales", C.c_void_p), ("scale_stride", C.c_uint64),
+                ("t_rows", C.c_void_p), ("t_row_stride", C.c_uint64), ("t_scales", C.c_void_p), ("t_scale_stride", C.c_uint64),
+                ("elems_per_rank", C.c_uint64), ("cols", C.c_uint64),
+                ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("shard_stride", C.c_uint64)]
+
+
+ADAMW_MX2D_GROUP_MAX = 16   # ALLRED_ADAMW_MX2D_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_mxfp8_2d covers
+
+
 class Seg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_uint64)]
 
@@ -258,6 +269,9 @@ SIGNATURES = [
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_mxfp8_2d", C.c_int,
+     [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    ("allred_plan_adamw_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

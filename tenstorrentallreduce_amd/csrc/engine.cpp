@@ -32,6 +32,7 @@
 
 #include "device_guard.hpp"
 #include "internal.hpp"
+#include "adamw_mx2d_ranges.hpp"
 #include "adamw_mx_ranges.hpp"
 #include "adamw_ranges.hpp"
 #include "mx2d_ranges.hpp"
@@ -1101,6 +1102,33 @@ int adamw_mx_check(const allred_plan* p, const allred_adamw_mx_bucket_f32* bucke
     }
 }
 
+// The checks of allred_plan_adamw_all_gather_shards_mxfp8_2d, all before any HIP call: the flags and
+// hyper, norm_sq and info as adamw_mx_check has them; the plan and the count; then
+// adamw_mx2d_ranges.hpp's rules for the list: mx2d_check's for the four outputs, the shape and the cap
+// of 2^31 - 1 squares, adamw_list_verdict's for the planes, the disjointness of up to four output
+// intervals, the plane blocks and the three small intervals, then the MX necessities.  dry: there is no
+// hyper to check.  hyper_bytes: 32 ngroups.
+int adamw_mx2d_check(const allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets, int count, const allred_adamw_hyper* hyper,
+                     const float* norm_sq, const float* info, int flags, bool dry = false,
+                     uint64_t hyper_bytes = kAdamwHyperBytes) {
+    if (!adamw_mx_pointers_ok(hyper, norm_sq, info, flags, dry)) return ALLRED_ERR_ARG;
+    if (!p || count < 0) return ALLRED_ERR_ARG;
+    if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
+    if (count > 0 && !buckets) return ALLRED_ERR_ARG;
+    std::vector<AdamwMx2dRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_adamw_mx2d_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = AdamwMx2dRange{Mx2dRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.t_rows, b.t_row_stride, b.t_scales,
+                                                     b.t_scale_stride, b.elems_per_rank, b.cols, b.param, b.shard_stride},
+                                           {b.grad, b.exp_avg, b.exp_avg_sq}};
+    }
+    switch (adamw_mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total, hyper, norm_sq, info, hyper_bytes)) {
+        case kAdamwMxOk: return ALLRED_OK;
+        case kAdamwMxUnsupported: return ALLRED_ERR_UNSUPPORTED;
+        default: return ALLRED_ERR_ARG;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1233,6 +1261,29 @@ int allred_plan_adamw_shards_mxfp8_launches(const allred_plan* p, const allred_a
     if (st != ALLRED_OK || count == 0) return st;
     return launch_adamw_group_mxfp8(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
                                     /*dry=*/true, nullptr);
+}
+
+// The group rules first, then adamw_mx2d_check with the whole hyper array as hyper's interval; all of it
+// before any HIP call.
+int allred_plan_adamw_all_gather_shards_mxfp8_2d(allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets,
+                                                 const uint8_t* group_of, int count, const allred_adamw_hyper* hyper, int ngroups,
+                                                 const float* norm_sq, float* info, int flags, void* stream) {
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_mx2d_check(p, buckets, count, hyper, norm_sq, info, flags, /*dry=*/false,
+                                    kAdamwHyperBytes * (uint64_t)ngroups);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_mxfp8_2d(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                       (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0, /*dry=*/false,
+                                       stream);
+}
+
+int allred_plan_adamw_shards_mxfp8_2d_launches(const allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets, int count) {
+    const int st = adamw_mx2d_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_adamw_group_mxfp8_2d(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
+                                       /*dry=*/true, nullptr);
 }
 
 int allred_plan_execute_group(allred_plan* p, const allred_bucket* buckets, int count, void* stream) {

@@ -136,6 +136,12 @@ int launch_ag_group_mxfp8_2d(const allred_mx2d_bucket_f32* buckets, int count, i
 int launch_adamw_group_mxfp8(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                              const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                              bool rceil, bool dry, void* stream);
+// a list of (checked) buckets of one fp32 matrix each, held as four planes (adamw_mx2d_kernels.hip):
+// launch_adamw_group_mxfp8's update, p' quantised to MXFP8 both row-wise (where a bucket has rows) and
+// column-wise into every rank's rows — k_adamw_ag_mxfp8_2d —, ALLRED_ADAMW_MX2D_GROUP_MAX buckets per launch.
+int launch_adamw_group_mxfp8_2d(const allred_adamw_mx2d_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                                const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                                bool rceil, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
