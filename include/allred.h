@@ -61,6 +61,8 @@ extern "C" {
  * Still ABI 7: allred_adamw_mx2d_bucket_f32, ALLRED_ADAMW_MX2D_GROUP_MAX and
  * allred_plan_adamw_all_gather_shards_mxfp8_2d / allred_plan_adamw_shards_mxfp8_2d_launches are additions — the
  * AdamW step inside that launch: both orientations of p', each rounded once from fp32.
+ * Still ABI 7: allred_plan_all_gather_shards_mxfp4 / allred_plan_all_gather_shards_mxfp4_launches are additions —
+ * the MXFP8 all-gather's call and bucket list with MXFP4 output: two e2m1 elements per row byte.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -718,6 +720,54 @@ typedef struct {                        /* 56 bytes */
 int allred_plan_all_gather_shards_mxfp8(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
                                         void* stream);
 int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
+/* MXFP4 ALL-GATHER FROM THE FP32 SHARDS: allred_plan_all_gather_shards_mxfp8 with OCP MXFP4 output, the
+ * narrowest of the three element widths the block-scaled f8f6f4 MFMA takes: every rank row receives the
+ * shard's values as e2m1 NIBBLES, two per byte, and the scale row one E8M0 byte per 32 elements — 0.53125
+ * bytes written per element instead of 1.03125, each value rounded once from the fp32 master.
+ * SHARED WITH THE MXFP8 CALL: the accepted plans, the ALLRED_MX_SCALE_RCEIL flag, allred_mx_bucket_f32 (one
+ * shard list serves both calls; `rows` then holds nibbles), the whole-tile rule (total >= 8,
+ * elems_per_rank % (256 * total) == 0), ALLRED_MX_GROUP_MAX = 32 buckets per launch and the scale rows:
+ * PLAIN LINEAR, the byte of elements e .. e + 31 of block b at (b * blk + e) / 32.  The kernel traces as
+ * k_ag_group_mxfp4<P, false|true> (csrc/mx4_kernels.hip; the bool: ALLRED_MX_SCALE_RCEIL).  No reference
+ * counterpart.
+ * ROWS: two elements per byte.  Element 2 i of a row is in bits 3:0 of byte i, element 2 i + 1 in bits
+ * 7:4 (the order of OCP MX and of v_cvt_scalef32_pk_fp4_f32).  Block b of EVERY rank row, rank b's
+ * included, receives blk / 2 bytes at byte b * blk / 2; a row's payload is elems_per_rank / 2 bytes.
+ * SEMANTICS.  Every output bit is a function of the input bits.  Per aligned group of 32 consecutive
+ * floats x_0 .. x_31 of block b (elements e .. e + 31, e % 32 == 0): 16 element bytes at byte
+ * (b * blk + e) / 2 of every row and one scale byte.
+ *   A = the largest bits(x_i) & 0x7fffffff, compared as integers.
+ *   A >= 0x7f800000 (a NaN or +-Inf in the block): scale byte 0xFF and all 16 element bytes 0x00.  E2M1
+ *     has no NaN encoding: the NaN scale makes the block NaN, and is the found-inf signal.
+ *   Otherwise:
+ *     E = (A >> 23) - 127                      (-127 for zero and for denormals)
+ *     X = E - 2                                (the floor rule of OCP MX v1.0: emax of e2m1 is 2), or, with
+ *         ALLRED_MX_SCALE_RCEIL, X = E - 2 + ((A & 0x7fffff) > 0x400000 ? 1 : 0): ceil(log2(amax / 6)),
+ *         under which no finite element saturates;
+ *     X is clamped below at -127 (the upper clamp cannot bind: X <= 126);   scale byte = X + 127.
+ *   y_i = x_i * 2^(-X): ONE fp32 multiply, denormals kept; 2^(-X) = (254 - scale byte) << 23 as fp32 bits,
+ *     a normal fp32 for every reachable byte.
+ *   nibble = y_i rounded to e2m1 by IEEE round to nearest, ties to the even code; the magnitudes 0, 0.5,
+ *     1, 1.5, 2, 3, 4, 6 are codes 0 .. 7 (so the ties 0.25, 0.75, 1.25, 1.75, 2.5, 3.5 and 5 give the
+ *     codes 0, 2, 2, 4, 4, 6 and 6);
+ *     |y_i| > 6 gives +-6; bit 3 is the sign, always kept: -0 and a negative value that rounds to zero
+ *     both give 0x8.
+ * Dequantised value = e2m1(nibble) * 2^(scale - 127).  Under ALLRED_MX_SCALE_RCEIL at E = 127 it can
+ * exceed fp32: a block whose amax is at or above 1.75 * 2^127 holds the element 4 at scale 2^126 (the
+ * MXFP8 call's 256 * 2^120).  The shard is only read.  Per row only elems_per_rank / 2 bytes of `rows`
+ * and elems_per_rank / 32 bytes of `scales` are written; every other byte keeps its bits.
+ * WHAT THE MI355X MAKES OF THE ROWS is NOT yet established: no test here feeds the nibble rows to the
+ * matrix core, so the lane map of the MXFP8 section is not claimed for them.
+ * CHECKS, all before any HIP call (a refused call writes nothing): those of the MXFP8 call with the row
+ * payload elems_per_rank / 2 — ALLRED_ERR_ARG for row_stride < elems_per_rank / 2 or % 16 != 0; every
+ * other rule, status and count == 0 as there.  DISJOINTNESS (csrc/mx_ranges.hpp, per_byte = 2): as
+ * there, byte-exact: rows of two buckets may abut at total * elems_per_rank / 2 bytes.
+ * LAUNCHES: as there — allred_plan_all_gather_shards_mxfp4_launches returns ceil(count / 32) or a negative
+ * status; the tables travel by value, so the call can be captured into a graph; one kernel form, no
+ * tune key; pipe_grid caps the grid. */
+int allred_plan_all_gather_shards_mxfp4(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                        void* stream);
+int allred_plan_all_gather_shards_mxfp4_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
 /* BOTH MXFP8 ORIENTATIONS FROM ONE PASS: allred_plan_all_gather_shards_mxfp8 for a weight that is used in
  * two GEMMs.  An MX block runs along the contraction dimension: Y = X W^T contracts over `in`, the columns
  * of W[out][in], and takes the rows above; the input-gradient GEMM dX = dY W contracts over `out` and

@@ -33,7 +33,7 @@ __all__ = [
     "ACC_BF16", "multi_plan", "run_multi", "TRANSPORT_RCCL", "TRANSPORT_PEER", "TRANSPORT_HOST", "MULTI_FLAT",
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
-    "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX", "mxfp8_dequantize",
+    "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX", "mxfp8_dequantize", "mxfp4_dequantize",
 ]
 
 
@@ -226,6 +226,25 @@ def mxfp8_dequantize(elements_u8, scales_u8) -> np.ndarray:
     mag = np.where(exp == 0, man * 2.0 ** -9, (1.0 + man / 8.0) * np.exp2((exp - 7).astype(np.float64)))
     val = np.where(e & 0x80, -mag, mag)
     val = np.where((e & 0x7F) == 0x7F, np.nan, val)
+    scale = np.where(s == 0xFF, np.nan, np.exp2(s.astype(np.float64) - 127.0))
+    with np.errstate(over="ignore"):
+        return (val * np.repeat(scale, 32, axis=-1)).astype(np.float32)
+
+
+def mxfp4_dequantize(elements_u8, scales_u8) -> np.ndarray:
+    """What Plan.all_gather_shards_mxfp4 wrote, as float32: e2m1(nibble) * 2^(scale - 127), element 2 i in
+    bits 3:0 of byte i and element 2 i + 1 in bits 7:4, the scale of element k being scales_u8[..., k // 32].
+    elements_u8: (..., n / 2) uint8, n % 32 == 0; scales_u8: (..., n / 32) uint8; the result is (..., n).
+    NaN for every element under a 0xFF scale (e2m1 has no NaN of its own).  Exact — every product is a
+    float32, denormals included — with one exception: under rceil a block whose amax is at or above
+    1.75 x 2^127 holds the element 4 at scale 2^126, which is +-Inf here."""
+    e = np.asarray(elements_u8, dtype=np.uint8)
+    s = np.asarray(scales_u8, dtype=np.uint8)
+    if e.shape[-1] % 16 or s.shape != e.shape[:-1] + (e.shape[-1] // 16,):
+        raise ValueError(f"elements {e.shape} and scales {s.shape} do not belong together")
+    nib = np.stack([e & 0xF, e >> 4], axis=-1).reshape(e.shape[:-1] + (2 * e.shape[-1],))
+    mag = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])[nib & 7]
+    val = np.where(nib & 8, -mag, mag)
     scale = np.where(s == 0xFF, np.nan, np.exp2(s.astype(np.float64) - 127.0))
     with np.errstate(over="ignore"):
         return (val * np.repeat(scale, 32, axis=-1)).astype(np.float32)
@@ -497,6 +516,25 @@ class Plan:
         st = lib.allred_plan_all_gather_shards_mxfp8_launches(self._h, arr, count)
         if st < 0:
             raise AllredError(st, "plan_all_gather_shards_mxfp8_launches")
+        return st
+
+    def all_gather_shards_mxfp4(self, buckets, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp4: all_gather_shards_mxfp8 on the same bucket tuples with OCP
+        MXFP4 output — TWO e2m1 elements per row byte (element 2 i in bits 3:0 of byte i), so a row's
+        payload and the least row_stride are elems_per_rank / 2 bytes; the scale rows are the MXFP8 call's.
+        One launch per ALLRED_MX_GROUP_MAX buckets; the shards are only read.  rceil: the scale exponent
+        rounded up (no finite element saturates).  mxfp4_dequantize gives the values back."""
+        arr, count = self._mx_buckets_f32(buckets)
+        flags = _lib.MX_SCALE_RCEIL if rceil else 0
+        check(lib.allred_plan_all_gather_shards_mxfp4(self._h, arr, count, flags, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp4")
+
+    def shards_mxfp4_launches(self, buckets) -> int:
+        """Kernel launches all_gather_shards_mxfp4 would enqueue for the list: one per ALLRED_MX_GROUP_MAX buckets."""
+        arr, count = self._mx_buckets_f32(buckets)
+        st = lib.allred_plan_all_gather_shards_mxfp4_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_all_gather_shards_mxfp4_launches")
         return st
 
     @staticmethod

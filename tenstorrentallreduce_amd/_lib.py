@@ -264,6 +264,8 @@ SIGNATURES = [
      [_P, C.POINTER(AdamwBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
+    ("allred_plan_all_gather_shards_mxfp4", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp8_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,

@@ -1033,8 +1033,10 @@ int adamw_check(const allred_plan* p, const allred_adamw_bucket_f32* buckets, in
 // the count as shards_f32_check has them; then mx_ranges.hpp's rules for the list — pointers,
 // alignments, sizes, strides, the tile cap, the disjointness of element rows, scale rows and shard
 // blocks (which also refuses address arithmetic that would overflow), and the one kernel form's shape.
+// per_byte = 2: those of allred_plan_all_gather_shards_mxfp4 — the same with a row payload of
+// elems_per_rank / 2 bytes.
 static_assert(kMxMaxTiles == kTileSpanMaxTiles, "mx_ranges.hpp's copy of tile_span.hpp's constant");
-int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags) {
+int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags, uint64_t per_byte = 1) {
     if (!mx_flags_ok(flags)) return ALLRED_ERR_ARG;
     if (!p || count < 0) return ALLRED_ERR_ARG;
     if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
@@ -1045,7 +1047,7 @@ int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int coun
         const allred_mx_bucket_f32& b = buckets[i];
         ranges[(size_t)i] = MxRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.elems_per_rank, b.shard, b.shard_stride};
     }
-    switch (mx_list_verdict(ranges.data(), count, (uint64_t)p->total)) {
+    switch (mx_list_verdict(ranges.data(), count, (uint64_t)p->total, per_byte)) {
         case kMxOk: return ALLRED_OK;
         case kMxUnsupported: return ALLRED_ERR_UNSUPPORTED;
         default: return ALLRED_ERR_ARG;
@@ -1146,6 +1148,21 @@ int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* p, const all
     const int st = mx_check(p, buckets, count, 0);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_ag_group_mxfp8(buckets, count, p->total, false, /*dry=*/true, nullptr);
+}
+
+int allred_plan_all_gather_shards_mxfp4(allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                        void* stream) {
+    const int st = mx_check(p, buckets, count, flags, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp4(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, /*dry=*/false, stream);
+}
+
+int allred_plan_all_gather_shards_mxfp4_launches(const allred_plan* p, const allred_mx_bucket_f32* buckets, int count) {
+    const int st = mx_check(p, buckets, count, 0, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_ag_group_mxfp4(buckets, count, p->total, false, /*dry=*/true, nullptr);
 }
 
 int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,

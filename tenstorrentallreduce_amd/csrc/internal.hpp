@@ -126,6 +126,10 @@ int launch_adamw_group_f32(const allred_adamw_bucket_f32* buckets, const uint8_t
 // (mx_kernels.hip): the shard quantised to MXFP8 into every rank's rows — k_ag_group_mxfp8 —,
 // ALLRED_MX_GROUP_MAX buckets per launch.  rceil: ALLRED_MX_SCALE_RCEIL.  dry: as above.
 int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+
+// The same list through allred_plan_all_gather_shards_mxfp4 (mx4_kernels.hip): the shard quantised to
+// MXFP4, two e2m1 elements per row byte — k_ag_group_mxfp4 —, ALLRED_MX_GROUP_MAX buckets per launch.
+int launch_ag_group_mxfp4(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
 // a list of (checked) buckets of one fp32 matrix each (mx2d_kernels.hip): the shard quantised to MXFP8
 // both row-wise (where a bucket has rows) and column-wise, as W^T, into every rank's rows —
 // k_ag_group_mxfp8_2d —, ALLRED_MX2D_GROUP_MAX buckets per launch.  rceil, dry: as above.

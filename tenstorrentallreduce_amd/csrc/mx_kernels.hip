@@ -23,21 +23,9 @@ namespace {
 
 constexpr int kMxGroupMax = ALLRED_MX_GROUP_MAX;   // buckets of one launch
 
-// The shard and the scale rows of every bucket of a launch: entry i for bucket i of the launch, block
-// b of the bucket at shard + b * stride floats, rank r's scale row at scales + r * scale_stride bytes.
-// GroupSpan carries the element rows: GroupBucket::ranks is the bucket's row 0 of BYTES and
-// GroupBucket::stride its row stride in BYTES here (this file alone reads them).  Two more words per
-// entry than GroupShardF32, hence 32 entries: 2064 + 1024 = 3088 bytes of kernel arguments.
-struct MxShard {           // 32 bytes
-    const float* shard;
-    uint64_t stride;       // floats
-    uint8_t* scales;
-    uint64_t scale_stride; // bytes
-};
-struct MxShards {
-    MxShard s[kMxGroupMax];   // entries past the last bucket: zero
-};
-static_assert(sizeof(MxShard) == 32 && sizeof(MxShards) == 32 * kMxGroupMax, "the kernel-argument layout");
+// MxShard / MxShards (mx_quant.hpp): the shard and the scale rows of every bucket of a launch.  GroupSpan
+// carries the element rows: GroupBucket::ranks is the bucket's row 0 of BYTES and GroupBucket::stride
+// its row stride in BYTES here (this file and mx4_kernels.hip alone read them so).
 static_assert(sizeof(GroupSpan) + sizeof(MxShards) < 4096, "kernel arguments stay below 4 KiB");
 static_assert(kMxGroupMax <= kGroupMax, "GroupSpan's table holds a launch");
 static_assert(sizeof(allred_mx_bucket_f32) == 56, "allred.h's layout");

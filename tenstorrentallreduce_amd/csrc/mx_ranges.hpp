@@ -18,6 +18,10 @@
 // Rows or scales may therefore sit in the gap of a wide shard_stride, and scale rows in the skew of
 // nobody: a skew belongs to its rows' interval.  The two doublings are checked: a list with one that
 // overflows is refused like any other address arithmetic that would.
+// allred_plan_all_gather_shards_mxfp4 takes the same list with TWO elements per row byte: `per_byte`
+// (1: MXFP8, the default; 2: MXFP4) divides the row payload, n / per_byte bytes, which row_stride must
+// cover and which the element rows' ShardRange carries; the scale rows, the shard and every other
+// rule are one element width's as the other's.  n % 8 == 0 keeps the payload even at per_byte 2.
 // Plain C++: engine.cpp includes it under hipcc, tests/test_mx_ranges.py under g++.
 #pragma once
 
@@ -42,11 +46,11 @@ struct MxRange {
 
 // the 2-byte view of the list, appended to *out (three entries per bucket); false when a doubling
 // overflows — *out is then unspecified
-inline bool mx_as_ranges(const MxRange* list, int count, std::vector<ShardRange>* out) {
+inline bool mx_as_ranges(const MxRange* list, int count, std::vector<ShardRange>* out, uint64_t per_byte = 1) {
     out->reserve(out->size() + 3 * (size_t)(count > 0 ? count : 0));
     for (int i = 0; i < count; ++i) {
         const MxRange& s = list[i];
-        out->push_back(ShardRange{s.rows, s.row_stride / 2, s.n / 2, nullptr, 0});
+        out->push_back(ShardRange{s.rows, s.row_stride / 2, s.n / per_byte / 2, nullptr, 0});
         out->push_back(ShardRange{s.scales, s.scale_stride / 2, s.n / 64, nullptr, 0});
         uint64_t n2, stride2;
         if (__builtin_mul_overflow(s.n, (uint64_t)2, &n2) || __builtin_mul_overflow(s.shard_stride, (uint64_t)2, &stride2))
@@ -58,11 +62,11 @@ inline bool mx_as_ranges(const MxRange* list, int count, std::vector<ShardRange>
 
 // true: every interval above lies in the address space and no two share a byte.  total >= 1; every n
 // a multiple of total, every row_stride and scale_stride even (the caller's checks).
-inline bool mx_lists_disjoint(const MxRange* list, int count, uint64_t total) {
+inline bool mx_lists_disjoint(const MxRange* list, int count, uint64_t total, uint64_t per_byte = 1) {
     if (count <= 0) return true;
     if (!list || total == 0) return false;
     std::vector<ShardRange> ranges;
-    if (!mx_as_ranges(list, count, &ranges)) return false;
+    if (!mx_as_ranges(list, count, &ranges, per_byte)) return false;
     return shard_lists_disjoint(ranges.data(), (int)ranges.size(), total);
 }
 
@@ -74,27 +78,27 @@ enum MxVerdict { kMxOk = 0, kMxArg, kMxUnsupported };
 inline bool mx_flags_ok(int flags) { return (flags & ~1) == 0; }
 
 // kMxArg: a NULL pointer; rows not 16-byte, scales not 8-byte, the shard not 16-byte aligned; n == 0
-// or not a multiple of 8 total (the grouped calls' rule for a rank row); row_stride < n or % 16 != 0;
+// or not a multiple of 8 total (the grouped calls' rule for a rank row); row_stride < n / per_byte or % 16 != 0;
 // scale_stride < n / 32 or % 8 != 0; shard_stride < blk or % 4 != 0; more than 2^31 - 1 tiles of 256
 // elements in the list; address arithmetic that would overflow; two intervals sharing a byte.  Then
 // kMxUnsupported for the whole list: a bucket that is not whole tiles (total < 8 or n % (256 total)).
-inline MxVerdict mx_list_verdict(const MxRange* list, int count, uint64_t total) {
+inline MxVerdict mx_list_verdict(const MxRange* list, int count, uint64_t total, uint64_t per_byte = 1) {
     if (count <= 0) return count < 0 ? kMxArg : kMxOk;
-    if (!list || total == 0) return kMxArg;
+    if (!list || total == 0 || (per_byte != 1 && per_byte != 2)) return kMxArg;
     uint64_t tiles = 0;
     for (int i = 0; i < count; ++i) {
         const MxRange& s = list[i];
         if (!s.rows || (uintptr_t)s.rows % 16 || !s.scales || (uintptr_t)s.scales % 8 || !s.shard || (uintptr_t)s.shard % 16)
             return kMxArg;
         if (s.n == 0 || total > UINT64_MAX / 8 || s.n % (8 * total)) return kMxArg;
-        if (s.row_stride < s.n || s.row_stride % 16) return kMxArg;
+        if (s.row_stride < s.n / per_byte || s.row_stride % 16) return kMxArg;
         if (s.scale_stride < s.n / 32 || s.scale_stride % 8) return kMxArg;
         if (s.shard_stride < s.n / total || s.shard_stride % 4) return kMxArg;
         const uint64_t t = s.n / 256 + (s.n % 256 ? 1 : 0);
         if (t > kMxMaxTiles - tiles) return kMxArg;
         tiles += t;
     }
-    if (!mx_lists_disjoint(list, count, total)) return kMxArg;
+    if (!mx_lists_disjoint(list, count, total, per_byte)) return kMxArg;
     for (int i = 0; i < count; ++i)
         if (total < 8 || list[i].n % (256 * total)) return kMxUnsupported;
     return kMxOk;
