@@ -63,6 +63,8 @@ extern "C" {
  * AdamW step inside that launch: both orientations of p', each rounded once from fp32.
  * Still ABI 7: allred_plan_all_gather_shards_mxfp4 / allred_plan_all_gather_shards_mxfp4_launches are additions —
  * the MXFP8 all-gather's call and bucket list with MXFP4 output: two e2m1 elements per row byte.
+ * Still ABI 7: allred_plan_adamw_all_gather_shards_mxfp4 / allred_plan_adamw_shards_mxfp4_launches are additions —
+ * the MXFP8 AdamW call's arguments and bucket list with MXFP4 rows: the MXFP4 step in two launches.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -907,6 +909,54 @@ int allred_plan_adamw_all_gather_shards_mxfp8(
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, void* stream);
 int allred_plan_adamw_shards_mxfp8_launches(const allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets, int count);
+/* ADAMW INSIDE THE MXFP4 ALL-GATHER: the call above with the rows of allred_plan_all_gather_shards_mxfp4 —
+ * the MXFP4 training step in TWO launches (allred_plan_reduce_scatter_shards_f32_norm, then this call).
+ * p' is quantised to e2m1 nibbles in the register it is computed in, once, from fp32: no bf16 rows that
+ * nobody reads and no second pass over the masters.
+ * SHARED WITH THE MXFP8 ADAMW CALL: allred_adamw_mx_bucket_f32 (one bucket list serves both calls; `rows`
+ * then holds nibbles), ALLRED_ADAMW_ZERO_GRAD, ALLRED_ADAMW_MX_RCEIL, ALLRED_ADAMW_MX_GROUP_MAX = 32 buckets
+ * per launch, group_of / ngroups / hyper / norm_sq / info and their rules, the accepted plans, the
+ * whole-tile rule (total >= 8, elems_per_rank % (256 * total) == 0), count == 0 (ALLRED_OK after the
+ * pointer and ngroups checks, nothing launched, info NOT written) and info written by the first launch
+ * alone.  The kernel traces as k_adamw_ag_mxfp4<P, false|true, false|true> (csrc/adamw_mx4_kernels.hip; the
+ * bools: ALLRED_ADAMW_ZERO_GRAD, ALLRED_ADAMW_MX_RCEIL).  No routing rule and no tune key; pipe_grid caps
+ * the grid.  No reference counterpart.
+ * SEMANTICS: the two sections composed.
+ *   PLANES.  param, exp_avg and exp_avg_sq receive exactly the p', m' and v' that
+ *   allred_plan_adamw_all_gather_shards_f32_groups stores (every operation ONE IEEE fp32 operation in the
+ *   stated order, never an fma); on a SKIPPED step (N non-finite) they keep their bits; with
+ *   ALLRED_ADAMW_ZERO_GRAD +0.0f is stored over every gradient element read, skipped or not.
+ *   ROWS.  Block b of EVERY rank's element row and scale row receives exactly what
+ *   allred_plan_all_gather_shards_mxfp4 writes from a shard that holds p' (p on a skipped step): per
+ *   aligned 32 elements A = the integer maximum of bits(p'_i) & 0x7fffffff, E = (A >> 23) - 127; X = E - 2
+ *   (the floor rule), or with ALLRED_ADAMW_MX_RCEIL X = E - 2 + ((A & 0x7fffff) > 0x400000 ? 1 : 0); X
+ *   clamped below at -127, scale byte = X + 127; y_i = p'_i * 2^(-X), ONE fp32 multiply; y_i rounded to
+ *   e2m1 by IEEE round to nearest, ties to the even code, +-6 on saturation, the sign always kept; a block
+ *   that holds a NaN or +-Inf gets scale byte 0xFF over 16 element bytes 0x00.
+ *   NIBBLE ORDER.  Element 2 i of a row is in bits 3:0 of byte i, element 2 i + 1 in bits 7:4; block b of a
+ *   row is blk / 2 bytes at byte b * blk / 2, a row's payload elems_per_rank / 2 bytes.
+ *   Everything else keeps its bits: stride skew, gaps, guards, memory past a row's payload.
+ * GUARANTEE (tests/test_gpu_adamw_mx4.py): the four planes are bit for bit those of
+ * allred_plan_adamw_all_gather_shards_f32_groups on the same inputs, and the element rows and scale rows
+ * bit for bit those of allred_plan_all_gather_shards_mxfp4 (same scale rule) run on the param plane that
+ * call leaves.
+ * WHAT THE MI355X MAKES OF THE ROWS is NOT yet established, as for allred_plan_all_gather_shards_mxfp4: no
+ * test here feeds the nibble rows to the matrix core.
+ * CHECKS, all before any HIP call (a refused call writes nothing): those of the MXFP8 AdamW call with the
+ * row payload elems_per_rank / 2 — ALLRED_ERR_ARG for row_stride < elems_per_rank / 2 or % 16 != 0; every
+ * other rule and status as there.  DISJOINTNESS (csrc/adamw_mx_ranges.hpp, per_byte = 2): as there,
+ * byte-exact; the element rows are still ONE interval [rows, rows + total * row_stride), so rows of two
+ * buckets may abut at total * elems_per_rank / 2 bytes.
+ * LAUNCHES: as there, 3920 bytes of kernel arguments — allred_plan_adamw_shards_mxfp4_launches returns
+ * ceil(count / 32), or a negative status for arguments the call would refuse (it takes no hyper).  The
+ * tables travel by value, so the call can be captured into a graph. */
+int allred_plan_adamw_all_gather_shards_mxfp4(
+    allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, void* stream);
+int allred_plan_adamw_shards_mxfp4_launches(const allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets, int count);
 /* ADAMW INSIDE THE 2D MXFP8 ALL-GATHER: the call above with the outputs of
  * allred_plan_all_gather_shards_mxfp8_2d — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call) with BOTH GEMM operands, the row-wise rows

@@ -581,6 +581,10 @@ class Plan:
         row and scale row as all_gather_shards_mxfp8 writes them — one launch per ALLRED_ADAMW_MX_GROUP_MAX
         buckets.  group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr and zero_grad: as the groups call
         (ngroups = 1 with group_of = None: one set); rceil: the scale exponent rounded up."""
+        self._adamw_mx_run("mxfp8", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
+
+    def _adamw_mx_run(self, fmt, buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream):
+        """allred_plan_adamw_all_gather_shards_<fmt>: the MXFP8 and the MXFP4 call take the same arguments"""
         arr, count = self._adamw_mx_buckets_f32(buckets)
         groups = None
         if group_of is not None:
@@ -590,10 +594,10 @@ class Plan:
                 raise ValueError("a group index is one byte")
             groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
         flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
-        check(lib.allred_plan_adamw_all_gather_shards_mxfp8(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups),
-                                                            int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None,
-                                                            flags, _stream_ptr(stream)),
-              "plan_adamw_all_gather_shards_mxfp8")
+        fn = getattr(lib, "allred_plan_adamw_all_gather_shards_" + fmt)
+        check(fn(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups), int(norm_sq_ptr or 0) or None,
+                 int(info_ptr or 0) or None, flags, _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_" + fmt)
 
     def adamw_shards_mxfp8_launches(self, buckets) -> int:
         """Kernel launches adamw_all_gather_shards_mxfp8 would enqueue for the list: one per
@@ -602,6 +606,23 @@ class Plan:
         st = lib.allred_plan_adamw_shards_mxfp8_launches(self._h, arr, count)
         if st < 0:
             raise AllredError(st, "plan_adamw_shards_mxfp8_launches")
+        return st
+
+    def adamw_all_gather_shards_mxfp4(self, buckets, group_of, hyper_ptr, ngroups: int, norm_sq_ptr=None, info_ptr=None,
+                                      zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp4: adamw_all_gather_shards_mxfp8 on the same bucket tuples
+        with OCP MXFP4 rows — the new parameters quantised once, from fp32, to e2m1 nibbles (two per byte,
+        element 2 i in the low nibble of byte i; row_stride >= elems_per_rank / 2) and E8M0 scale bytes, as
+        all_gather_shards_mxfp4 writes them.  The other arguments: as adamw_all_gather_shards_mxfp8."""
+        self._adamw_mx_run("mxfp4", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
+
+    def adamw_shards_mxfp4_launches(self, buckets) -> int:
+        """Kernel launches adamw_all_gather_shards_mxfp4 would enqueue for the list: one per
+        ALLRED_ADAMW_MX_GROUP_MAX buckets, whatever the groups."""
+        arr, count = self._adamw_mx_buckets_f32(buckets)
+        st = lib.allred_plan_adamw_shards_mxfp4_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_adamw_shards_mxfp4_launches")
         return st
 
     @staticmethod

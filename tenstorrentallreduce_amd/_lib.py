@@ -271,6 +271,9 @@ SIGNATURES = [
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_mxfp4", C.c_int,
+     [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    ("allred_plan_adamw_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp8_2d", C.c_int,
      [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),

@@ -1,6 +1,7 @@
 // adamw_body.hpp — the ONE AdamW body of the fp32-shard calls, adamw_ag, with its kernel-argument
 // tables: included by adamw_kernels.hip (k_adamw_ag_group_f32, k_adamw_ag_groups_f32: bf16 rank rows)
-// and adamw_mx_kernels.hip (k_adamw_ag_mxfp8: MXFP8 element rows and E8M0 scale rows).  The output
+// adamw_mx_kernels.hip (k_adamw_ag_mxfp8: MXFP8 element rows and E8M0 scale rows) and
+// adamw_mx4_kernels.hip (k_adamw_ag_mxfp4: MXFP4 nibble rows and E8M0 scale rows).  The output
 // stage — what wave 0 puts into the LDS slot for p' and what every wave stores from it — is a
 // compile-time choice (AdamwOut); everything else is the same code in every instance.
 #pragma once
@@ -49,10 +50,14 @@ static_assert(sizeof(allred_adamw_hyper) == 32 && sizeof(allred_adamw_bucket_f32
 //   kOutMxFloor  MXFP8, the floor scale rule: 4 e4m3 bytes per lane and the tile's 8 E8M0 bytes, a
 //   kOutMxRceil  272-byte slot, 8-byte row stores and one 8-byte scale store per rank row (RCEIL: the
 //                rounded-up scale of allred.h).
-enum AdamwOut { kOutBf16 = 0, kOutMxFloor, kOutMxRceil };
+//   kOutMx4Floor MXFP4: 2 bytes of e2m1 nibbles per lane and the tile's 8 E8M0 bytes, a 144-byte slot,
+//   kOutMx4Rceil 8-byte row stores in k_ag_group_mxfp4's split (four rows per store instruction) and
+//                one 8-byte scale store per rank row.
+enum AdamwOut { kOutBf16 = 0, kOutMxFloor, kOutMxRceil, kOutMx4Floor, kOutMx4Rceil };
 // The scale rows of every bucket of an MXFP8 launch: rank r's scale row at scales + r * scale_stride
 // bytes.  GroupSpan then carries the ELEMENT rows in bytes (GroupBucket::ranks row 0, ::stride the
-// row stride in bytes), as in mx_kernels.hip.  The bf16 kernels hand adamw_ag an AdamwNoScales.
+// row stride in bytes), as in mx_kernels.hip; the MXFP4 stage takes the same table.  The bf16 kernels
+// hand adamw_ag an AdamwNoScales.
 struct AdamwMxScaleRows {   // 16 bytes
     uint8_t* scales;
     uint64_t scale_stride;  // bytes
@@ -63,7 +68,8 @@ struct AdamwMxScales {
 struct AdamwNoScales {};
 static_assert(sizeof(AdamwMxScales) == 16 * kAdamwGroupMax, "the kernel-argument layout");
 // the LDS slot of one tile: 64 lanes' 8 bytes of bf16, or 64 lanes' 4 element bytes, the tile's 8 scale
-// bytes at byte 256 and 8 bytes of padding (272: a multiple of 16, so that both slots are 16-byte aligned)
+// bytes at byte 256 and 8 bytes of padding (272: a multiple of 16, so that both slots are 16-byte aligned),
+// or 64 lanes' 2 nibble bytes, the 8 scale bytes at byte 128 and 8 bytes of padding (144, likewise)
 template <AdamwOut OUT>
 struct AdamwSlot {
     typedef uint2 type[2][64];
@@ -75,6 +81,14 @@ struct AdamwSlot<kOutMxFloor> {
 template <>
 struct AdamwSlot<kOutMxRceil> {
     typedef uint32_t type[2][68];
+};
+template <>
+struct AdamwSlot<kOutMx4Floor> {
+    typedef uint32_t type[2][36];
+};
+template <>
+struct AdamwSlot<kOutMx4Rceil> {
+    typedef uint32_t type[2][36];
 };
 
 // the value lane `g` of this wave holds in x, as a wave-uniform (scalar) value; g is wave-uniform
@@ -168,14 +182,40 @@ __device__ __forceinline__ PerGroup per_group(const allred_adamw_hyper& h) {
 //   behind the barrier every wave reads column c's 8 bytes and stores them nontemporally to its rows
 //   (row stride in BYTES), lanes < RPW read the 8 scale bytes and store them to scale row RPW w + lane
 //   with a PLAIN store (mx_kernels.hip says why); wave 0's plane stores follow as before.
+// OUT == kOutMx4Floor / kOutMx4Rceil (MXFP4 rows), allred.h's rule for allred_plan_all_gather_shards_mxfp4
+// applied to p' in wave 0's registers.  In front of the barrier the stage is the MXFP8 one with other
+// constants — the same eight-lane block and three DPP steps, the scale byte (A >> 23) - 2 (RCEIL: + 1
+// above mantissa 0x400000), one v_mul_f32 per element, v_med3_f32 with +-6 and two
+// v_cvt_scalef32_pk_fp4_f32 at scale 1.0 (mx_quant.hpp cvt2_fp4<0>, <1>): lane l's four nibbles are 16
+// bits, element 4 l in bits 3:0; 0x0000 and scale 0xFF for a block with a NaN or Inf.
+//   slot (144 bytes): bytes 2 l, 2 l + 1 = lane l's nibbles, ONE ds_write_b16 per lane under the full exec
+//   mask (the other form — a fourth DPP step that hands the odd lane's 16 bits to the even lane, which
+//   writes a dword — costs a DPP move, a shift-or and an exec change for the same 128 bytes; neither is
+//   measured); bytes 128 .. 135 = the tile's eight scale bytes, byte writes from lanes 0, 8 .. 56 as
+//   above; bytes 136 .. 143 padding, never read.
+//   behind the barrier the split is k_ag_group_mxfp4's, not the one above: c = lane % 16, q = lane / 16,
+//   a wave reads column c's 8 bytes and stores them nontemporally to rows RPW w + 4 k + q at byte
+//   local * 128 + 8 c — a row's 128 bytes are one run from 16 lanes and one store instruction covers
+//   FOUR rows —, so W = min(4, P / 4) waves store RPW = P / W rows each; lanes < RPW of a storing wave
+//   write the scale bytes with a PLAIN store as above.
+//   P = 8: W = 2, waves 2 and 3 have no rows.  k_ag_group_mxfp4 lets them return before their first
+//   load; it has no barrier.  Here NO wave leaves before the workgroup's last barrier: waves 2 and 3
+//   walk every tile and arrive at every lds_barrier, and skip the LDS read and the stores only (w < W, a
+//   scalar branch).  The one early return stays the workgroup-uniform `mine <= 0`.  The slot-rotation
+//   argument above therefore carries over unchanged: a wave without rows has no LDS read to protect,
+//   and a wave with rows has passed the barrier of tile j + 1 behind its read of tile j as before.
 // ---------------------------------------------------------------------------
 template <int P, bool ZERO, bool GROUPS, AdamwOut OUT = kOutBf16, class Scales = AdamwNoScales>
 __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup& planes, const AdamwGroupOf& group_of,
                                          const allred_adamw_hyper* __restrict__ hyper, int ngroups,
                                          const float* __restrict__ norm_sq, float* info, const Scales& scale_rows = Scales{}) {
-    constexpr int TV = 32, RPI = 2, RPW = P / 4, OPS = RPW / RPI;
-    constexpr bool MX = OUT != kOutBf16;
-    static_assert(OPS >= 1, "P >= 8");
+    constexpr bool MX4 = OUT == kOutMx4Floor || OUT == kOutMx4Rceil;
+    constexpr bool MX = OUT != kOutBf16;   // any MX row format: element rows in bytes, and scale rows
+    constexpr bool RCEIL = OUT == kOutMxRceil || OUT == kOutMx4Rceil;
+    // TV: lanes of a row's run; RPI: rows per store instruction; W: waves with rows (MX4 at P = 8: two)
+    constexpr int TV = MX4 ? 16 : 32, RPI = 64 / TV, W = (MX4 && P / RPI < 4) ? P / RPI : 4, RPW = P / W, OPS = RPW / RPI;
+    constexpr int SC = MX4 ? 32 : 64;   // the slot's dword that holds the tile's scale bytes
+    static_assert(OPS >= 1 && RPW * W == P && OPS * RPI == RPW, "P >= 8, whole store instructions per wave");
     static_assert(std::is_same<Scales, AdamwMxScales>::value == MX, "the scale rows come with the MXFP8 output stage");
     __shared__ __attribute__((aligned(16))) typename AdamwSlot<OUT>::type slot;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -205,15 +245,16 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
         const GroupTile gt = group_span_at(span, group_span_tile(span, blockIdx.x, (uint32_t)j), cursor);
         const GroupBucket& e = span.b[gt.bucket];
         return Tile{e.ranks, e.stride, (uint64_t)gt.local * TV,
-                    (uint64_t)gt.block * planes.s[gt.bucket].stride + (uint64_t)gt.rem * (8 * TV), gt.bucket, group_at(gt.bucket)};
+                    (uint64_t)gt.block * planes.s[gt.bucket].stride + (uint64_t)gt.rem * 256, gt.bucket, group_at(gt.bucket)};
     };
     const int mine = (int)group_span_mine(span, blockIdx.x);
     if (mine <= 0) return;   // the whole workgroup: no barrier is left waiting
     const int last = mine - 1;
     auto rows = [&](const Tile& t, int j) {
         if constexpr (MX) {
+            if (W < 4 && w >= W) return;   // MX4 at P = 8: a wave without rows, behind the barrier (scalar branch)
             const uint2 v = reinterpret_cast<const uint2*>(&slot[j & 1][0])[c];
-            const uint2 sc = reinterpret_cast<const uint2*>(&slot[j & 1][64])[0];
+            const uint2 sc = reinterpret_cast<const uint2*>(&slot[j & 1][SC])[0];
             uint8_t* row0 = reinterpret_cast<uint8_t*>(t.ranks);
 #pragma unroll
             for (int k = 0; k < OPS; ++k) {
@@ -317,14 +358,20 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
             A = max_dpp<0x4E>(A);    // quad_perm [2, 3, 0, 1]: lane ^ 2
             A = max_dpp<0x141>(A);   // row_half_mirror: a lane of the other quad of the 8
             const bool special = A >= 0x7f800000u;
-            int sb = (int)(A >> 23) - 8;
-            if constexpr (OUT == kOutMxRceil) sb += (A & 0x7fffffu) > 0x600000u ? 1 : 0;
+            int sb = (int)(A >> 23) - (MX4 ? 2 : 8);   // emax of e2m1 is 2, of e4m3 8
+            if constexpr (RCEIL) sb += (A & 0x7fffffu) > (MX4 ? 0x400000u : 0x600000u) ? 1 : 0;
             sb = sb > 0 ? sb : 0;
             const float inv = __uint_as_float((uint32_t)(254 - sb) << 23);
-            uint32_t e = cvt2<false>(y.p[0] * inv, y.p[1] * inv, 0u);
-            e = cvt2<true>(y.p[2] * inv, y.p[3] * inv, e);
-            slot[j & 1][lane] = special ? 0x7f7f7f7fu : e;
-            if ((lane & 7) == 0) reinterpret_cast<uint8_t*>(&slot[j & 1][64])[lane >> 3] = (uint8_t)(special ? 0xffu : (uint32_t)sb);
+            if constexpr (MX4) {
+                uint32_t e = cvt2_fp4<0>(y.p[0] * inv, y.p[1] * inv, 0u);
+                e = cvt2_fp4<1>(y.p[2] * inv, y.p[3] * inv, e);   // bits 31:16 stay zero
+                reinterpret_cast<uint16_t*>(&slot[j & 1][0])[lane] = (uint16_t)(special ? 0u : e);
+            } else {
+                uint32_t e = cvt2<false>(y.p[0] * inv, y.p[1] * inv, 0u);
+                e = cvt2<true>(y.p[2] * inv, y.p[3] * inv, e);
+                slot[j & 1][lane] = special ? 0x7f7f7f7fu : e;
+            }
+            if ((lane & 7) == 0) reinterpret_cast<uint8_t*>(&slot[j & 1][SC])[lane >> 3] = (uint8_t)(special ? 0xffu : (uint32_t)sb);
         } else {
             slot[j & 1][lane] = make_uint2(pack_rne(y.p[0], y.p[1]), pack_rne(y.p[2], y.p[3]));
         }

@@ -21,6 +21,10 @@
 // a plane {nullptr, 0, n, plane, shard_stride} — and hits_bucket tests each of the three against them,
 // as adamw_lists_disjoint does: rows, scales and the three small buffers may lie in the gap of a wide
 // shard_stride.
+// allred_plan_adamw_all_gather_shards_mxfp4 takes the same list with TWO elements per row byte: `per_byte`
+// (1: MXFP8, the default; 2: MXFP4) divides the row payload, n / per_byte bytes, which row_stride must
+// cover and which the element rows' ShardRange carries, as in mx_ranges.hpp; the scale rows, the planes,
+// the small buffers and every other rule are one element width's as the other's.
 // Plain C++: engine.cpp includes it under hipcc, tests/test_adamw_mx_ranges.py under g++.
 #pragma once
 
@@ -44,11 +48,11 @@ struct AdamwMxRange {
 
 // the 2-byte view of the list, appended to *out (six entries per bucket); false when a doubling
 // overflows — *out is then unspecified
-inline bool adamw_mx_as_ranges(const AdamwMxRange* list, int count, std::vector<ShardRange>* out) {
+inline bool adamw_mx_as_ranges(const AdamwMxRange* list, int count, std::vector<ShardRange>* out, uint64_t per_byte = 1) {
     out->reserve(out->size() + 6 * (size_t)(count > 0 ? count : 0));
     for (int i = 0; i < count; ++i) {
         const AdamwMxRange& s = list[i];
-        out->push_back(ShardRange{s.rows, s.row_stride / 2, s.n / 2, nullptr, 0});
+        out->push_back(ShardRange{s.rows, s.row_stride / 2, s.n / per_byte / 2, nullptr, 0});
         out->push_back(ShardRange{s.scales, s.scale_stride / 2, s.n / 64, nullptr, 0});
         uint64_t n2, stride2;
         if (__builtin_mul_overflow(s.n, (uint64_t)2, &n2) || __builtin_mul_overflow(s.shard_stride, (uint64_t)2, &stride2))
@@ -62,10 +66,10 @@ inline bool adamw_mx_as_ranges(const AdamwMxRange* list, int count, std::vector<
 // multiple of total, every row_stride and scale_stride even, every plane non-null (the caller's checks).
 // hyper / norm_sq / info: nullptr = not given.  hyper_bytes: the length of hyper's interval.
 inline bool adamw_mx_lists_disjoint(const AdamwMxRange* list, int count, uint64_t total, const void* hyper, const void* norm_sq,
-                                    const void* info, uint64_t hyper_bytes = kAdamwHyperBytes) {
+                                    const void* info, uint64_t hyper_bytes = kAdamwHyperBytes, uint64_t per_byte = 1) {
     if (count > 0 && (!list || total == 0)) return false;
     std::vector<ShardRange> ranges;
-    if (!adamw_mx_as_ranges(list, count, &ranges)) return false;
+    if (!adamw_mx_as_ranges(list, count, &ranges, per_byte)) return false;
     if (!shard_lists_disjoint(ranges.data(), (int)ranges.size(), total)) return false;
     uint64_t bytes;
     if (__builtin_mul_overflow(total, (uint64_t)4, &bytes)) return false;
@@ -105,13 +109,14 @@ inline bool adamw_mx_pointers_ok(const void* hyper, const void* norm_sq, const v
 }
 
 // kAdamwMxArg: a NULL pointer; rows not 16-byte, scales not 8-byte, a plane not 16-byte aligned; n == 0
-// or not a multiple of 8 total; row_stride < n or % 16 != 0; scale_stride < n / 32 or % 8 != 0;
+// or not a multiple of 8 total; row_stride < n / per_byte or % 16 != 0; per_byte not 1 or 2; scale_stride < n / 32 or % 8 != 0;
 // shard_stride < blk or % 4 != 0; more than 2^31 - 1 tiles of 256 elements in the list; address
 // arithmetic that would overflow; two intervals sharing a byte.  Then kAdamwMxUnsupported for the whole
 // list: a bucket that is not whole tiles (total < 8 or n % (256 total)).
 inline AdamwMxVerdict adamw_mx_list_verdict(const AdamwMxRange* list, int count, uint64_t total, const void* hyper,
-                                            const void* norm_sq, const void* info, uint64_t hyper_bytes = kAdamwHyperBytes) {
-    if (count < 0) return kAdamwMxArg;
+                                            const void* norm_sq, const void* info, uint64_t hyper_bytes = kAdamwHyperBytes,
+                                            uint64_t per_byte = 1) {
+    if (count < 0 || (per_byte != 1 && per_byte != 2)) return kAdamwMxArg;
     if (count > 0 && (!list || total == 0)) return kAdamwMxArg;
     uint64_t tiles = 0;
     for (int i = 0; i < count; ++i) {
@@ -120,14 +125,14 @@ inline AdamwMxVerdict adamw_mx_list_verdict(const AdamwMxRange* list, int count,
         for (const void* q : s.plane)
             if (!q || (uintptr_t)q % 16) return kAdamwMxArg;
         if (s.n == 0 || total > UINT64_MAX / 8 || s.n % (8 * total)) return kAdamwMxArg;
-        if (s.row_stride < s.n || s.row_stride % 16) return kAdamwMxArg;
+        if (s.row_stride < s.n / per_byte || s.row_stride % 16) return kAdamwMxArg;
         if (s.scale_stride < s.n / 32 || s.scale_stride % 8) return kAdamwMxArg;
         if (s.shard_stride < s.n / total || s.shard_stride % 4) return kAdamwMxArg;
         const uint64_t t = s.n / 256 + (s.n % 256 ? 1 : 0);
         if (t > kMxMaxTiles - tiles) return kAdamwMxArg;
         tiles += t;
     }
-    if (!adamw_mx_lists_disjoint(list, count, total, hyper, norm_sq, info, hyper_bytes)) return kAdamwMxArg;
+    if (!adamw_mx_lists_disjoint(list, count, total, hyper, norm_sq, info, hyper_bytes, per_byte)) return kAdamwMxArg;
     for (int i = 0; i < count; ++i)
         if (total < 8 || list[i].n % (256 * total)) return kAdamwMxUnsupported;
     return kAdamwMxOk;

@@ -140,6 +140,11 @@ int launch_ag_group_mxfp8_2d(const allred_mx2d_bucket_f32* buckets, int count, i
 int launch_adamw_group_mxfp8(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                              const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                              bool rceil, bool dry, void* stream);
+// The same list through allred_plan_adamw_all_gather_shards_mxfp4 (adamw_mx4_kernels.hip): the same update,
+// p' quantised to MXFP4, two e2m1 elements per row byte — k_adamw_ag_mxfp4 —, as many buckets per launch.
+int launch_adamw_group_mxfp4(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                             const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                             bool rceil, bool dry, void* stream);
 // a list of (checked) buckets of one fp32 matrix each, held as four planes (adamw_mx2d_kernels.hip):
 // launch_adamw_group_mxfp8's update, p' quantised to MXFP8 both row-wise (where a bucket has rows) and
 // column-wise into every rank's rows — k_adamw_ag_mxfp8_2d —, ALLRED_ADAMW_MX2D_GROUP_MAX buckets per launch.
