@@ -65,6 +65,9 @@ extern "C" {
  * the MXFP8 all-gather's call and bucket list with MXFP4 output: two e2m1 elements per row byte.
  * Still ABI 7: allred_plan_adamw_all_gather_shards_mxfp4 / allred_plan_adamw_shards_mxfp4_launches are additions —
  * the MXFP8 AdamW call's arguments and bucket list with MXFP4 rows: the MXFP4 step in two launches.
+ * Still ABI 7: ALLRED_MX4_2D_GROUP_MAX and allred_plan_all_gather_shards_mxfp4_2d /
+ * allred_plan_all_gather_shards_mxfp4_2d_launches are additions — the 2D call's bucket list with MXFP4 output
+ * in both orientations, written in strips that cross shard blocks.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -834,6 +837,48 @@ typedef struct {                        /* 96 bytes */
 int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count, int flags,
                                            void* stream);
 int allred_plan_all_gather_shards_mxfp8_2d_launches(const allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count);
+/* BOTH MXFP4 ORIENTATIONS FROM ONE PASS: allred_plan_all_gather_shards_mxfp8_2d with OCP MXFP4 output — to
+ * that call what allred_plan_all_gather_shards_mxfp4 is to allred_plan_all_gather_shards_mxfp8.  It takes
+ * the same allred_mx2d_bucket_f32 list (one shard list serves both calls; rows and t_rows then hold e2m1
+ * NIBBLES, two per byte), the same plans and the ALLRED_MX_SCALE_RCEIL flag.  The kernel traces as
+ * k_ag_group_mxfp4_2d<P, false|true, false|true> (csrc/mx4_2d_kernels.hip; the bools: ALLRED_MX_SCALE_RCEIL,
+ * a bucket of the launch has rows).  No reference counterpart.
+ * SEMANTICS.  Every output bit is a function of the input bits.  The bucket is the matrix W[nrows][cols]
+ * in `total` shard blocks of R = nrows / total rows, as in the MXFP8 2D call.
+ *   ROW-WISE, when rows != NULL: rows and scales receive exactly what allred_plan_all_gather_shards_mxfp4
+ *   writes for the same shard and flag.
+ *   COLUMN-WISE, always: for every column j and every aligned group of 32 rows 32 g .. 32 g + 31 take
+ *   x_k = W[32 g + k][j] and apply to x_0 .. x_31 the MXFP4 rule stated above for 32 consecutive floats —
+ *   the integer amax A; scale byte 0xFF over sixteen 0x00 element bytes for a NaN or Inf in the block; the
+ *   floor or ALLRED_MX_SCALE_RCEIL exponent for emax 2, clamped below at -127; ONE fp32 multiply by 2^(-X),
+ *   denormals kept; saturating round to nearest even onto e2m1, the sign always kept.
+ *   The nibble of W[i][j] is ELEMENT j * nrows + i of EVERY rank's t row: byte (j * nrows + i) / 2, bits 3:0
+ *   for even i and bits 7:4 for odd i (nrows is even).  The scale byte of the group goes to byte
+ *   j * (nrows / 32) + g of EVERY rank's t scale row.
+ * A t row is therefore the plain linear MXFP4 row of W^T[cols][nrows]: byte k of a t scale row belongs to
+ * elements 32 k .. 32 k + 31, bytes 16 k .. 16 k + 15, of the t element row, and allred's mxfp4 dequantiser
+ * (e2m1(nibble) * 2^(scale - 127)) gives W^T back within the format's error.  Per rank only
+ * elems_per_rank / 2 bytes of t_rows (and of rows) and elems_per_rank / 32 bytes of t_scales (and of scales)
+ * are written; every other byte keeps its bits.  The shard is only read.
+ * WHAT THE MI355X MAKES OF THE ROWS is NOT yet established, as for allred_plan_all_gather_shards_mxfp4: the
+ * nibble order is OCP MX's and v_cvt_scalef32_pk_fp4_f32's; no test here feeds nibble rows, row-wise or t, to
+ * the matrix core, so the lane map of the MXFP8 section is not claimed for them.
+ * CHECKS, all before any HIP call (a refused call writes nothing): those of
+ * allred_plan_all_gather_shards_mxfp8_2d with the element payload halved — ALLRED_ERR_ARG for row_stride
+ * (when rows are given) or t_row_stride < elems_per_rank / 2 or % 16 != 0; every other rule and status as
+ * there, ALLRED_ERR_UNSUPPORTED for the WHOLE list for the MX necessities only (total < 8, cols % 32 != 0,
+ * nrows % (32 * total) != 0); count == 0: ALLRED_OK, nothing launched.  DISJOINTNESS (csrc/mx2d_ranges.hpp,
+ * per_byte = 2): as there, byte-exact and block-exact over the four output intervals of `total` strides each
+ * and the shard blocks.
+ * LAUNCHES: ONE launch covers ALLRED_MX4_2D_GROUP_MAX = 21 buckets (96 bytes of table per bucket: 4080
+ * bytes of kernel arguments, below 4 KiB), in list order: allred_plan_all_gather_shards_mxfp4_2d_launches
+ * returns ceil(count / 21), or a negative status for arguments the call would refuse.  The tables travel
+ * by value, so the call can be captured into a graph.  One kernel form, no routing rule and no tune key;
+ * pipe_grid caps the grid like every persistent pass. */
+#define ALLRED_MX4_2D_GROUP_MAX 21      /* buckets one launch of allred_plan_all_gather_shards_mxfp4_2d covers */
+int allred_plan_all_gather_shards_mxfp4_2d(allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count, int flags,
+                                           void* stream);
+int allred_plan_all_gather_shards_mxfp4_2d_launches(const allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count);
 /* ADAMW INSIDE THE MXFP8 ALL-GATHER: allred_plan_adamw_all_gather_shards_f32_groups with the rows of
  * allred_plan_all_gather_shards_mxfp8 — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call), as the bf16 step is.  p' is quantised

@@ -564,6 +564,25 @@ class Plan:
             raise AllredError(st, "plan_all_gather_shards_mxfp8_2d_launches")
         return st
 
+    def all_gather_shards_mxfp4_2d(self, buckets, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp4_2d: all_gather_shards_mxfp8_2d on the same bucket tuples with OCP
+        MXFP4 output in both orientations — e2m1 nibbles, two per byte, so row_stride and t_row_stride cover
+        elems_per_rank / 2 bytes.  rows / scales (where given) are what all_gather_shards_mxfp4 writes; the t rows
+        are W^T as linear MXFP4 rows, written in strips that cross shard blocks.  One launch per
+        ALLRED_MX4_2D_GROUP_MAX buckets.  mxfp4_dequantize on the t rows gives W^T back."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        flags = _lib.MX_SCALE_RCEIL if rceil else 0
+        check(lib.allred_plan_all_gather_shards_mxfp4_2d(self._h, arr, count, flags, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp4_2d")
+
+    def shards_mxfp4_2d_launches(self, buckets) -> int:
+        """Kernel launches all_gather_shards_mxfp4_2d would enqueue for the list: one per ALLRED_MX4_2D_GROUP_MAX buckets."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        st = lib.allred_plan_all_gather_shards_mxfp4_2d_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_all_gather_shards_mxfp4_2d_launches")
+        return st
+
     @staticmethod
     def _adamw_mx_buckets_f32(buckets):
         """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, elems_per_rank, param_ptr, grad_ptr,

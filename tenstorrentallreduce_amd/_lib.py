@@ -179,6 +179,7 @@ class Mx2dBucketF32(C.Structure):   # allred_mx2d_bucket_f32: MxBucketF32's rows
 
 
 MX2D_GROUP_MAX = 21   # ALLRED_MX2D_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8_2d covers
+MX4_2D_GROUP_MAX = 21   # ALLRED_MX4_2D_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp4_2d covers
 
 
 class AdamwMxBucketF32(C.Structure):   # allred_adamw_mx_bucket_f32: MxBucketF32's rows and scales, AdamwBucketF32's four planes
@@ -268,6 +269,8 @@ SIGNATURES = [
     ("allred_plan_all_gather_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp8_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
+    ("allred_plan_all_gather_shards_mxfp4_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
+    ("allred_plan_all_gather_shards_mxfp4_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),

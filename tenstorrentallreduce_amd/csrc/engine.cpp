@@ -1058,7 +1058,9 @@ int mx_check(const allred_plan* p, const allred_mx_bucket_f32* buckets, int coun
 // mx2d_ranges.hpp's rules for the list — the row-wise outputs optional, the t outputs, the matrix
 // shape, the cap on the work items, the disjointness of up to four output intervals and the shard
 // blocks (which also refuses address arithmetic that would overflow), then the MX necessities.
-int mx2d_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags) {
+// per_byte = 2: those of allred_plan_all_gather_shards_mxfp4_2d — the same with a payload of
+// elems_per_rank / 2 bytes in rows and t_rows.
+int mx2d_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags, uint64_t per_byte = 1) {
     if (!mx2d_flags_ok(flags)) return ALLRED_ERR_ARG;
     if (!p || count < 0) return ALLRED_ERR_ARG;
     if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
@@ -1070,7 +1072,7 @@ int mx2d_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int 
         ranges[(size_t)i] = Mx2dRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.t_rows, b.t_row_stride, b.t_scales,
                                       b.t_scale_stride, b.elems_per_rank, b.cols, b.shard, b.shard_stride};
     }
-    switch (mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total)) {
+    switch (mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total, per_byte)) {
         case kMx2dOk: return ALLRED_OK;
         case kMx2dUnsupported: return ALLRED_ERR_UNSUPPORTED;
         default: return ALLRED_ERR_ARG;
@@ -1179,6 +1181,21 @@ int allred_plan_all_gather_shards_mxfp8_2d_launches(const allred_plan* p, const 
     const int st = mx2d_check(p, buckets, count, 0);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_ag_group_mxfp8_2d(buckets, count, p->total, false, /*dry=*/true, nullptr);
+}
+
+int allred_plan_all_gather_shards_mxfp4_2d(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,
+                                           void* stream) {
+    const int st = mx2d_check(p, buckets, count, flags, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp4_2d(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, /*dry=*/false, stream);
+}
+
+int allred_plan_all_gather_shards_mxfp4_2d_launches(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count) {
+    const int st = mx2d_check(p, buckets, count, 0, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_ag_group_mxfp4_2d(buckets, count, p->total, false, /*dry=*/true, nullptr);
 }
 
 int allred_plan_reduce_scatter_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {

@@ -134,6 +134,10 @@ int launch_ag_group_mxfp4(const allred_mx_bucket_f32* buckets, int count, int to
 // both row-wise (where a bucket has rows) and column-wise, as W^T, into every rank's rows —
 // k_ag_group_mxfp8_2d —, ALLRED_MX2D_GROUP_MAX buckets per launch.  rceil, dry: as above.
 int launch_ag_group_mxfp8_2d(const allred_mx2d_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+// The same list through allred_plan_all_gather_shards_mxfp4_2d (mx4_2d_kernels.hip): both orientations as
+// MXFP4, two e2m1 elements per byte, in strips across shard blocks — k_ag_group_mxfp4_2d —,
+// ALLRED_MX4_2D_GROUP_MAX buckets per launch.
+int launch_ag_group_mxfp4_2d(const allred_mx2d_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
 // a list of (checked) whole-tile buckets with their four fp32 planes, element rows and scale rows
 // (adamw_mx_kernels.hip): launch_adamw_group_f32's update with ngroups >= 1 parameter groups, p' quantised
 // to MXFP8 into every rank's rows — k_adamw_ag_mxfp8 —, ALLRED_ADAMW_MX_GROUP_MAX buckets per launch.  dry: as above.

@@ -77,14 +77,18 @@ inline bool mx2d_flags_ok(int flags) { return mx_flags_ok(flags); }
 
 // kMx2dArg: exactly one of rows and scales nullptr; t_rows, t_scales or shard nullptr; rows, t_rows or the
 // shard not 16-byte, scales or t_scales not 8-byte aligned; n == 0 or not a multiple of 8 total; cols == 0
-// or n % cols != 0; a row stride < n or % 16 != 0; a scale stride < n / 32 or % 8 != 0; shard_stride < blk
+// or n % cols != 0; a row stride < n / per_byte or % 16 != 0; a scale stride < n / 32 or % 8 != 0; shard_stride < blk
 // or % 4 != 0; more than 2^31 - 1 squares of 1024 elements in the list (the work items of every patch
 // shape are at most these); address arithmetic that would overflow; two intervals sharing a byte.  Then
 // kMx2dUnsupported for the whole list, the MX necessities: total < 8, cols % 32 != 0 or
 // nrows % (32 total) != 0 in a bucket.
-inline Mx2dVerdict mx2d_list_verdict(const Mx2dRange* list, int count, uint64_t total) {
+// allred_plan_all_gather_shards_mxfp4_2d takes the same list with TWO elements per byte of rows and t_rows:
+// `per_byte` (1: MXFP8, the default; 2: MXFP4) divides the payload, n / per_byte bytes, that row_stride and
+// t_row_stride must cover, as it does in mx_list_verdict.  The four row intervals are total strides long
+// whatever the payload, so the disjointness rule above serves both; n % 8 == 0 keeps the payload even.
+inline Mx2dVerdict mx2d_list_verdict(const Mx2dRange* list, int count, uint64_t total, uint64_t per_byte = 1) {
     if (count <= 0) return count < 0 ? kMx2dArg : kMx2dOk;
-    if (!list || total == 0) return kMx2dArg;
+    if (!list || total == 0 || (per_byte != 1 && per_byte != 2)) return kMx2dArg;
     uint64_t squares = 0;
     for (int i = 0; i < count; ++i) {
         const Mx2dRange& s = list[i];
@@ -94,8 +98,8 @@ inline Mx2dVerdict mx2d_list_verdict(const Mx2dRange* list, int count, uint64_t 
             return kMx2dArg;
         if (s.n == 0 || total > UINT64_MAX / 8 || s.n % (8 * total)) return kMx2dArg;
         if (s.cols == 0 || s.n % s.cols) return kMx2dArg;
-        if (s.rows && (s.row_stride < s.n || s.row_stride % 16 || s.scale_stride < s.n / 32 || s.scale_stride % 8)) return kMx2dArg;
-        if (s.t_row_stride < s.n || s.t_row_stride % 16 || s.t_scale_stride < s.n / 32 || s.t_scale_stride % 8) return kMx2dArg;
+        if (s.rows && (s.row_stride < s.n / per_byte || s.row_stride % 16 || s.scale_stride < s.n / 32 || s.scale_stride % 8)) return kMx2dArg;
+        if (s.t_row_stride < s.n / per_byte || s.t_row_stride % 16 || s.t_scale_stride < s.n / 32 || s.t_scale_stride % 8) return kMx2dArg;
         if (s.shard_stride < s.n / total || s.shard_stride % 4) return kMx2dArg;
         const uint64_t q = s.n / 1024 + (s.n % 1024 ? 1 : 0);
         if (q > kMxMaxTiles - squares) return kMx2dArg;
