@@ -68,6 +68,9 @@ extern "C" {
  * Still ABI 7: ALLRED_MX4_2D_GROUP_MAX and allred_plan_all_gather_shards_mxfp4_2d /
  * allred_plan_all_gather_shards_mxfp4_2d_launches are additions — the 2D call's bucket list with MXFP4 output
  * in both orientations, written in strips that cross shard blocks.
+ * Still ABI 7: ALLRED_ADAMW_MX4_2D_GROUP_MAX and allred_plan_adamw_all_gather_shards_mxfp4_2d /
+ * allred_plan_adamw_shards_mxfp4_2d_launches are additions — the AdamW step inside that launch: both MXFP4
+ * orientations of p', each rounded once from fp32, on allred_adamw_mx2d_bucket_f32's list.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -1080,6 +1083,55 @@ int allred_plan_adamw_all_gather_shards_mxfp8_2d(
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, void* stream);
 int allred_plan_adamw_shards_mxfp8_2d_launches(const allred_plan* plan, const allred_adamw_mx2d_bucket_f32* buckets, int count);
+/* ADAMW INSIDE THE 2D MXFP4 ALL-GATHER: the call above with the outputs of
+ * allred_plan_all_gather_shards_mxfp4_2d — the MXFP4 training step in TWO launches
+ * (allred_plan_reduce_scatter_shards_f32_norm, then this call) with BOTH GEMM operands as e2m1 nibbles, each
+ * rounded ONCE from the fp32 p' in the register it is computed in.  No third launch and no second read of
+ * the masters.
+ * SHARED WITH THE MXFP8 2D ADAMW CALL: allred_adamw_mx2d_bucket_f32 (one bucket list serves both calls; rows
+ * and t_rows then hold nibbles, two per byte; rows = scales = NULL: the column-wise outputs only),
+ * ALLRED_ADAMW_ZERO_GRAD, ALLRED_ADAMW_MX_RCEIL, group_of / ngroups / hyper / norm_sq / info and their rules,
+ * the accepted plans, count == 0 (ALLRED_OK after the pointer and ngroups checks, nothing launched, info NOT
+ * written) and info written by the first launch alone.  The kernel traces as
+ * k_adamw_ag_mxfp4_2d<P, false|true, false|true, false|true> (csrc/adamw_mx4_2d_kernels.hip; the bools:
+ * ALLRED_ADAMW_ZERO_GRAD, ALLRED_ADAMW_MX_RCEIL, a bucket of the launch has rows).  No routing rule and no
+ * tune key; pipe_grid caps the grid like every persistent pass.  No reference counterpart.
+ * SEMANTICS: the two sections composed; every output bit is a function of the input bits.
+ *   PLANES.  param, exp_avg and exp_avg_sq receive exactly the p', m' and v' that
+ *   allred_plan_adamw_all_gather_shards_f32_groups stores (every operation ONE IEEE fp32 operation in the
+ *   stated order, never an fma); on a SKIPPED step (N non-finite) they keep their bits (they are not
+ *   written); with ALLRED_ADAMW_ZERO_GRAD +0.0f is stored over every gradient element read, skipped or not.
+ *   OUTPUTS.  rows / scales (when given), t_rows and t_scales of EVERY rank receive exactly what
+ *   allred_plan_all_gather_shards_mxfp4_2d writes from a shard that holds p' (p on a skipped step;
+ *   ALLRED_ADAMW_MX_RCEIL: with ALLRED_MX_SCALE_RCEIL): row-wise the MXFP4 rule for 32 consecutive floats of
+ *   a row, column-wise the same rule for x_k = p'[32 g + k][j], the nibble at element j * nrows + 32 g + k
+ *   of the t row, the scale byte at j * (nrows / 32) + g of the t scale row.  Both are rounded from the fp32
+ *   p', neither from the other.
+ *   Everything else keeps its bits: stride skew, gaps, guards, memory past a row's payload.
+ * GUARANTEE (tests/test_gpu_adamw_mx4_2d.py): for every bucket the four planes are bit for bit those of
+ * allred_plan_adamw_all_gather_shards_f32_groups on the same inputs, and the four outputs are bit for bit
+ * those of allred_plan_all_gather_shards_mxfp4_2d (same scale rule) run on the param plane that call leaves;
+ * on a skipped step the outputs are the quantisation of p.
+ * CHECKS, all before any HIP call (a refused call writes nothing): those of the MXFP8 2D AdamW call with the
+ * element payload halved — ALLRED_ERR_ARG for row_stride (when rows are given) or t_row_stride <
+ * elems_per_rank / 2 or % 16 != 0; every other rule and status as there, ALLRED_ERR_UNSUPPORTED for the WHOLE
+ * list for the MX necessities only (total < 8, cols % 32 != 0, nrows % (32 * total) != 0).  They give
+ * nrows % 256 == 0, all the kernel's strips of four or eight row groups need: no refusal of its own.
+ * DISJOINTNESS (csrc/adamw_mx2d_ranges.hpp, per_byte = 2): as there, byte-exact and block-exact over the up to
+ * four output intervals of `total` strides each, the four planes' blocks and the three small buffers.
+ * LAUNCHES: ALLRED_ADAMW_MX4_2D_GROUP_MAX = 16 buckets each (120 bytes of table and one group byte per
+ * bucket: 4032 bytes of kernel arguments, below 4 KiB; seventeen pass it), in list order, whatever the
+ * groups are: allred_plan_adamw_shards_mxfp4_2d_launches returns ceil(count / 16), or a negative status for
+ * arguments the call would refuse (it takes no hyper).  The tables travel by value, so the call can be
+ * captured into a graph; hyper is rewritten by the caller between replays. */
+#define ALLRED_ADAMW_MX4_2D_GROUP_MAX 16 /* buckets one launch of this call covers */
+int allred_plan_adamw_all_gather_shards_mxfp4_2d(
+    allred_plan* plan, const allred_adamw_mx2d_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, void* stream);
+int allred_plan_adamw_shards_mxfp4_2d_launches(const allred_plan* plan, const allred_adamw_mx2d_bucket_f32* buckets, int count);
 /* Device-side profiling of the schedule form (the reference's DeviceZoneScopedN
  * "ALL_RED_LOOP", allred_BO_2D/kernels/dataflow_kernel.cpp:147, dumped by
  * DumpDeviceProfileResults, allred_helper.hpp:88).  stamp_words: the uint64

@@ -661,6 +661,10 @@ class Plan:
         parameters quantised once, from fp32, into BOTH orientations as all_gather_shards_mxfp8_2d writes
         them: the row-wise rows (where given) and the column-wise rows of every rank.  One launch per
         ALLRED_ADAMW_MX2D_GROUP_MAX buckets.  The other arguments: as adamw_all_gather_shards_mxfp8."""
+        self._adamw_mx2d_run("mxfp8_2d", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
+
+    def _adamw_mx2d_run(self, fmt, buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream):
+        """allred_plan_adamw_all_gather_shards_<fmt>: the MXFP8 and the MXFP4 2D call take the same arguments"""
         arr, count = self._adamw_mx2d_buckets_f32(buckets)
         groups = None
         if group_of is not None:
@@ -670,10 +674,10 @@ class Plan:
                 raise ValueError("a group index is one byte")
             groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
         flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
-        check(lib.allred_plan_adamw_all_gather_shards_mxfp8_2d(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups),
-                                                               int(norm_sq_ptr or 0) or None, int(info_ptr or 0) or None,
-                                                               flags, _stream_ptr(stream)),
-              "plan_adamw_all_gather_shards_mxfp8_2d")
+        fn = getattr(lib, "allred_plan_adamw_all_gather_shards_" + fmt)
+        check(fn(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups), int(norm_sq_ptr or 0) or None,
+                 int(info_ptr or 0) or None, flags, _stream_ptr(stream)),
+              "plan_adamw_all_gather_shards_" + fmt)
 
     def adamw_shards_mxfp8_2d_launches(self, buckets) -> int:
         """Kernel launches adamw_all_gather_shards_mxfp8_2d would enqueue for the list: one per
@@ -682,6 +686,24 @@ class Plan:
         st = lib.allred_plan_adamw_shards_mxfp8_2d_launches(self._h, arr, count)
         if st < 0:
             raise AllredError(st, "plan_adamw_shards_mxfp8_2d_launches")
+        return st
+
+    def adamw_all_gather_shards_mxfp4_2d(self, buckets, group_of, hyper_ptr, ngroups: int, norm_sq_ptr=None, info_ptr=None,
+                                         zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp4_2d: adamw_all_gather_shards_mxfp8_2d on the same bucket
+        tuples with OCP MXFP4 outputs — the new parameters quantised once, from fp32, to e2m1 nibbles in BOTH
+        orientations (two per byte; row_stride and t_row_stride >= elems_per_rank / 2) and E8M0 scale bytes,
+        as all_gather_shards_mxfp4_2d writes them.  One launch per ALLRED_ADAMW_MX4_2D_GROUP_MAX buckets.  The
+        other arguments: as adamw_all_gather_shards_mxfp8_2d."""
+        self._adamw_mx2d_run("mxfp4_2d", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
+
+    def adamw_shards_mxfp4_2d_launches(self, buckets) -> int:
+        """Kernel launches adamw_all_gather_shards_mxfp4_2d would enqueue for the list: one per
+        ALLRED_ADAMW_MX4_2D_GROUP_MAX buckets, whatever the groups."""
+        arr, count = self._adamw_mx2d_buckets_f32(buckets)
+        st = lib.allred_plan_adamw_shards_mxfp4_2d_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_adamw_shards_mxfp4_2d_launches")
         return st
 
     def rank_zones(self, stamps: np.ndarray):

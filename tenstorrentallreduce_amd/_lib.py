@@ -202,6 +202,7 @@ class AdamwMx2dBucketF32(C.Structure):   # allred_adamw_mx2d_bucket_f32: Mx2dBuc
 
 
 ADAMW_MX2D_GROUP_MAX = 16   # ALLRED_ADAMW_MX2D_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_mxfp8_2d covers
+ADAMW_MX4_2D_GROUP_MAX = 16   # ALLRED_ADAMW_MX4_2D_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_mxfp4_2d covers
 
 
 class Seg(C.Structure):
@@ -280,6 +281,9 @@ SIGNATURES = [
     ("allred_plan_adamw_all_gather_shards_mxfp8_2d", C.c_int,
      [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_mxfp4_2d", C.c_int,
+     [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
+    ("allred_plan_adamw_shards_mxfp4_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),
     ("allred_plan_stamp_words", C.c_uint64, [_P]),
     ("allred_plan_execute_profiled", C.c_int, [_P, _u16p, C.c_uint64, _P, _P, _P]),
     ("allred_plan_rank_zones", C.c_int, [_P, _P, _P, _P]),

@@ -66,8 +66,13 @@ inline bool adamw_mx2d_lists_disjoint(const AdamwMx2dRange* list, int count, uin
 // outputs, n, cols, shard_stride and the cap of 2^31 - 1 squares; two intervals sharing a byte or address
 // arithmetic that would overflow.  Then kAdamwMxUnsupported for the whole list: the 2D call's MX
 // necessities (total < 8, cols % 32 != 0, nrows % (32 total) != 0).
+// allred_plan_adamw_all_gather_shards_mxfp4_2d takes the same list with TWO elements per byte of rows and
+// t_rows: `per_byte` (1: MXFP8, the default; 2: MXFP4) is mx2d_list_verdict's, the payload n / per_byte bytes
+// that row_stride and t_row_stride must cover.  The row intervals are total strides long whatever the
+// payload, so the disjointness rule above serves both.
 inline AdamwMxVerdict adamw_mx2d_list_verdict(const AdamwMx2dRange* list, int count, uint64_t total, const void* hyper,
-                                              const void* norm_sq, const void* info, uint64_t hyper_bytes = kAdamwHyperBytes) {
+                                              const void* norm_sq, const void* info, uint64_t hyper_bytes = kAdamwHyperBytes,
+                                              uint64_t per_byte = 1) {
     if (count < 0) return kAdamwMxArg;
     if (count > 0 && (!list || total == 0)) return kAdamwMxArg;
     std::vector<Mx2dRange> outs((size_t)count);
@@ -76,7 +81,7 @@ inline AdamwMxVerdict adamw_mx2d_list_verdict(const AdamwMx2dRange* list, int co
             if (!q || (uintptr_t)q % 16) return kAdamwMxArg;
         outs[(size_t)i] = list[i].out;   // its NULL or misaligned .shard is mx2d_list_verdict's to refuse
     }
-    const Mx2dVerdict shape = mx2d_list_verdict(outs.data(), count, total);
+    const Mx2dVerdict shape = mx2d_list_verdict(outs.data(), count, total, per_byte);
     if (shape == kMx2dArg) return kAdamwMxArg;
     if (!adamw_mx2d_lists_disjoint(list, count, total, hyper, norm_sq, info, hyper_bytes)) return kAdamwMxArg;
     return shape == kMx2dOk ? kAdamwMxOk : kAdamwMxUnsupported;

@@ -1112,10 +1112,12 @@ int adamw_mx_check(const allred_plan* p, const allred_adamw_mx_bucket_f32* bucke
 // adamw_mx2d_ranges.hpp's rules for the list: mx2d_check's for the four outputs, the shape and the cap
 // of 2^31 - 1 squares, adamw_list_verdict's for the planes, the disjointness of up to four output
 // intervals, the plane blocks and the three small intervals, then the MX necessities.  dry: there is no
-// hyper to check.  hyper_bytes: 32 ngroups.
+// hyper to check.  hyper_bytes: 32 ngroups.  per_byte = 2: the checks of
+// allred_plan_adamw_all_gather_shards_mxfp4_2d — the same with a payload of elems_per_rank / 2 bytes in rows
+// and t_rows.
 int adamw_mx2d_check(const allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets, int count, const allred_adamw_hyper* hyper,
                      const float* norm_sq, const float* info, int flags, bool dry = false,
-                     uint64_t hyper_bytes = kAdamwHyperBytes) {
+                     uint64_t hyper_bytes = kAdamwHyperBytes, uint64_t per_byte = 1) {
     if (!adamw_mx_pointers_ok(hyper, norm_sq, info, flags, dry)) return ALLRED_ERR_ARG;
     if (!p || count < 0) return ALLRED_ERR_ARG;
     if (p->desc.variant != ALLRED_BO || p->desc.exec != ALLRED_EXEC_FUSED) return ALLRED_ERR_UNSUPPORTED;
@@ -1127,7 +1129,7 @@ int adamw_mx2d_check(const allred_plan* p, const allred_adamw_mx2d_bucket_f32* b
                                                      b.t_scale_stride, b.elems_per_rank, b.cols, b.param, b.shard_stride},
                                            {b.grad, b.exp_avg, b.exp_avg_sq}};
     }
-    switch (adamw_mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total, hyper, norm_sq, info, hyper_bytes)) {
+    switch (adamw_mx2d_list_verdict(ranges.data(), count, (uint64_t)p->total, hyper, norm_sq, info, hyper_bytes, per_byte)) {
         case kAdamwMxOk: return ALLRED_OK;
         case kAdamwMxUnsupported: return ALLRED_ERR_UNSUPPORTED;
         default: return ALLRED_ERR_ARG;
@@ -1341,6 +1343,30 @@ int allred_plan_adamw_shards_mxfp8_2d_launches(const allred_plan* p, const allre
     const int st = adamw_mx2d_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_adamw_group_mxfp8_2d(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
+                                       /*dry=*/true, nullptr);
+}
+
+// allred_plan_adamw_all_gather_shards_mxfp8_2d's checks with the MXFP4 payload (per_byte = 2), all of it
+// before any HIP call.  The strips of k_adamw_ag_mxfp4_2d need nrows % 256 == 0, which total >= 8 and
+// nrows % (32 total) == 0 give: no refusal of its own.
+int allred_plan_adamw_all_gather_shards_mxfp4_2d(allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets,
+                                                 const uint8_t* group_of, int count, const allred_adamw_hyper* hyper, int ngroups,
+                                                 const float* norm_sq, float* info, int flags, void* stream) {
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_mx2d_check(p, buckets, count, hyper, norm_sq, info, flags, /*dry=*/false,
+                                    kAdamwHyperBytes * (uint64_t)ngroups, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_mxfp4_2d(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                       (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0, /*dry=*/false,
+                                       stream);
+}
+
+int allred_plan_adamw_shards_mxfp4_2d_launches(const allred_plan* p, const allred_adamw_mx2d_bucket_f32* buckets, int count) {
+    const int st = adamw_mx2d_check(p, buckets, count, nullptr, nullptr, nullptr, 0, /*dry=*/true, kAdamwHyperBytes, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_adamw_group_mxfp4_2d(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
                                        /*dry=*/true, nullptr);
 }
 

@@ -155,6 +155,12 @@ int launch_adamw_group_mxfp4(const allred_adamw_mx_bucket_f32* buckets, const ui
 int launch_adamw_group_mxfp8_2d(const allred_adamw_mx2d_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                                 const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                                 bool rceil, bool dry, void* stream);
+// The same list through allred_plan_adamw_all_gather_shards_mxfp4_2d (adamw_mx4_2d_kernels.hip): the same
+// update, both orientations of p' as MXFP4, in strips across shard blocks — k_adamw_ag_mxfp4_2d —,
+// ALLRED_ADAMW_MX4_2D_GROUP_MAX buckets per launch.
+int launch_adamw_group_mxfp4_2d(const allred_adamw_mx2d_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                                const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                                bool rceil, bool dry, void* stream);
 int launch_rs_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
                    const int16_t* d_blocks, int blocks_per_rank, size_t block_elems, void* stream);
 int launch_ag_step(uint16_t* ranks, uint64_t stride, int total, const int16_t* d_partner,
