@@ -71,6 +71,8 @@ extern "C" {
  * Still ABI 7: ALLRED_ADAMW_MX4_2D_GROUP_MAX and allred_plan_adamw_all_gather_shards_mxfp4_2d /
  * allred_plan_adamw_shards_mxfp4_2d_launches are additions — the AdamW step inside that launch: both MXFP4
  * orientations of p', each rounded once from fp32, on allred_adamw_mx2d_bucket_f32's list.
+ * Still ABI 7: allred_plan_all_gather_shards_mxfp4_rht and allred_plan_adamw_all_gather_shards_mxfp4_rht are
+ * additions — the two 1D MXFP4 calls with a random Hadamard rotation of every MX block in front of the quantiser.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -776,6 +778,33 @@ int allred_plan_all_gather_shards_mxfp8_launches(const allred_plan* plan, const 
 int allred_plan_all_gather_shards_mxfp4(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
                                         void* stream);
 int allred_plan_all_gather_shards_mxfp4_launches(const allred_plan* plan, const allred_mx_bucket_f32* buckets, int count);
+/* MXFP4 ALL-GATHER WITH A RANDOM HADAMARD ROTATION: allred_plan_all_gather_shards_mxfp4 with every MX block
+ * rotated in front of the quantiser — a fixed sign flip per position, then the normalised 32-point Hadamard
+ * matrix — as the published MXFP4 training recipes rotate the GEMM operand: no outlier uses up its block's
+ * E8M0 scale, and with the activations rotated the same way the products are unchanged.  The rotation runs
+ * in the registers that hold the fp32 master values anyway: no pass over the masters before the call and none
+ * over every rank's copy after it.  The bucket list, the flags, the checks, the rows' and scale rows' layout,
+ * the nibble order and count == 0 are allred_plan_all_gather_shards_mxfp4's; sign_mask is one word per call and
+ * every value of it is valid.  The kernel traces as k_ag_group_mxfp4_rht<P, false|true>
+ * (csrc/mx4_rht_kernels.hip).  No reference counterpart, no tune key, no _launches twin: the call enqueues what
+ * allred_plan_all_gather_shards_mxfp4_launches returns for the same list.
+ * THE ROTATION binds every implementation bit for bit.  Per MX block — 32 consecutive fp32 values x[0 .. 31],
+ * the blocks the MXFP4 call scales:
+ *   1. SIGNS.  If bit i of sign_mask is set, the sign bit of x[i] is flipped (bits ^ 0x80000000): NaNs and
+ *      zeros included.
+ *   2. BUTTERFLY.  For h = 1, 2, 4, 8, 16, in that order, and every i with (i & h) == 0:
+ *      (x[i], x[i + h]) <- (x[i] + x[i + h], x[i] - x[i + h]).  Each operation is ONE IEEE fp32 addition or
+ *      subtraction, rounded to nearest even; denormals are kept and nothing is fused.
+ *   3. NORMALISATION.  Every value is multiplied by the fp32 constant 0x3E3504F3 (2^-2.5 rounded to nearest):
+ *      ONE IEEE multiply.  Output k is then 2^-2.5 * sum_i (-1)^popcount(i & k) * s_i * x_i.  The matrix is
+ *      symmetric and orthonormal: the same butterfly and constant FOLLOWED by the signs invert it.
+ *   4. QUANTISER.  The MXFP4 rule above (floor, or ALLRED_MX_SCALE_RCEIL) on the 32 rotated values.  If any
+ *      ROTATED value is a NaN or +-Inf the block gets scale byte 0xFF over 16 element bytes 0x00 — a block of
+ *      finite values whose butterfly overflows included (the largest finite fp32 plus a value three binades
+ *      below it is already +Inf), and a block with one NaN or Inf always (every output depends on every input).
+ * No matrix instruction computes this: the order of the additions is part of the contract. */
+int allred_plan_all_gather_shards_mxfp4_rht(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                            uint32_t sign_mask, void* stream);
 /* BOTH MXFP8 ORIENTATIONS FROM ONE PASS: allred_plan_all_gather_shards_mxfp8 for a weight that is used in
  * two GEMMs.  An MX block runs along the contraction dimension: Y = X W^T contracts over `in`, the columns
  * of W[out][in], and takes the rows above; the input-gradient GEMM dX = dY W contracts over `out` and
@@ -1005,6 +1034,22 @@ int allred_plan_adamw_all_gather_shards_mxfp4(
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, void* stream);
 int allred_plan_adamw_shards_mxfp4_launches(const allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets, int count);
+/* ADAMW INSIDE THE ROTATED MXFP4 ALL-GATHER: allred_plan_adamw_all_gather_shards_mxfp4 with the rows of
+ * allred_plan_all_gather_shards_mxfp4_rht.  Every argument, flag, check and status is that call's; sign_mask
+ * (any value) stands in front of stream.  The kernel traces as k_adamw_ag_mxfp4_rht<P, false|true, false|true>
+ * (csrc/adamw_mx4_rht_kernels.hip).
+ * GUARANTEE (tests/test_gpu_adamw_mx4_rht.py): the four planes and info come out bit for bit as
+ * allred_plan_adamw_all_gather_shards_mxfp4 leaves them — the rotation touches a copy of p' alone —, and the
+ * element rows and scale rows bit for bit as allred_plan_all_gather_shards_mxfp4_rht (same scale rule, same
+ * sign_mask) writes them from the param plane this call leaves: p', or p on a skipped step.
+ * LAUNCHES: no _launches twin; the call enqueues what allred_plan_adamw_shards_mxfp4_launches returns for the
+ * same list, with 3928 bytes of kernel arguments, and can be captured into a graph. */
+int allred_plan_adamw_all_gather_shards_mxfp4_rht(
+    allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, uint32_t sign_mask, void* stream);
 /* ADAMW INSIDE THE 2D MXFP8 ALL-GATHER: the call above with the outputs of
  * allred_plan_all_gather_shards_mxfp8_2d — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call) with BOTH GEMM operands, the row-wise rows

@@ -34,6 +34,7 @@ __all__ = [
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
     "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX", "mxfp8_dequantize", "mxfp4_dequantize",
+    "hadamard32",
 ]
 
 
@@ -248,6 +249,29 @@ def mxfp4_dequantize(elements_u8, scales_u8) -> np.ndarray:
     scale = np.where(s == 0xFF, np.nan, np.exp2(s.astype(np.float64) - 127.0))
     with np.errstate(over="ignore"):
         return (val * np.repeat(scale, 32, axis=-1)).astype(np.float32)
+
+
+def hadamard32(x, sign_mask: int, inverse: bool = False) -> np.ndarray:
+    """allred.h's rotation of Plan.all_gather_shards_mxfp4_rht on the host, float32 operation for float32
+    operation: per 32 consecutive values of the last axis, the sign of element i flipped where bit i of sign_mask
+    is set, the butterfly stages h = 1, 2, 4, 8, 16 — (x[i], x[i + h]) <- (x[i] + x[i + h], x[i] - x[i + h]) —,
+    then one multiply by 2^-2.5 (0x3E3504F3).  inverse=True: the butterfly and the constant, THEN the signs —
+    the transform is symmetric and orthonormal, so this undoes it up to rounding.  x: (..., 32 k); float32 out."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape[-1] % 32:
+        raise ValueError(f"the last axis of {x.shape} is no multiple of 32")
+    signs = (((int(sign_mask) & 0xFFFFFFFF) >> np.arange(32, dtype=np.uint64)) & 1).astype(np.uint32) << np.uint32(31)
+    v = x.reshape(-1, 32)
+    if not inverse:
+        v = (v.view(np.uint32) ^ signs).view(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for h in (1, 2, 4, 8, 16):
+            w = v.reshape(-1, 16 // h, 2, h)   # element i = (a, b, c): i = 2 h a + h b + c, b the bit h of i
+            v = np.stack([w[:, :, 0] + w[:, :, 1], w[:, :, 0] - w[:, :, 1]], axis=2).reshape(-1, 32)
+        v = v * np.uint32(0x3E3504F3).view(np.float32)
+    if inverse:
+        v = (v.view(np.uint32) ^ signs).view(np.float32)
+    return v.reshape(x.shape)
 
 
 # ---------------------------------------------------------------- device
@@ -537,6 +561,17 @@ class Plan:
             raise AllredError(st, "plan_all_gather_shards_mxfp4_launches")
         return st
 
+    def all_gather_shards_mxfp4_rht(self, buckets, sign_mask: int, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp4_rht: all_gather_shards_mxfp4 with every MX block of 32 fp32 values
+        rotated in front of the quantiser — the sign of element i flipped where bit i of sign_mask (32 bits) is
+        set, then the normalised 32-point Hadamard transform, every fp32 operation in allred.h's order.
+        hadamard32 is the same rule on the host; mxfp4_dequantize of the rows, then hadamard32(..., inverse=True),
+        gives the values back.  As many launches as shards_mxfp4_launches says."""
+        arr, count = self._mx_buckets_f32(buckets)
+        flags = _lib.MX_SCALE_RCEIL if rceil else 0
+        check(lib.allred_plan_all_gather_shards_mxfp4_rht(self._h, arr, count, flags, int(sign_mask) & 0xFFFFFFFF, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp4_rht")
+
     @staticmethod
     def _mx2d_buckets_f32(buckets):
         """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, t_rows_ptr, t_row_stride, t_scales_ptr,
@@ -602,8 +637,10 @@ class Plan:
         (ngroups = 1 with group_of = None: one set); rceil: the scale exponent rounded up."""
         self._adamw_mx_run("mxfp8", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
 
-    def _adamw_mx_run(self, fmt, buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream):
-        """allred_plan_adamw_all_gather_shards_<fmt>: the MXFP8 and the MXFP4 call take the same arguments"""
+    def _adamw_mx_run(self, fmt, buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream,
+                      sign_mask=None):
+        """allred_plan_adamw_all_gather_shards_<fmt>: the MXFP8 and the MXFP4 call take the same arguments, the
+        rotated MXFP4 call sign_mask in front of the stream"""
         arr, count = self._adamw_mx_buckets_f32(buckets)
         groups = None
         if group_of is not None:
@@ -614,8 +651,9 @@ class Plan:
             groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
         flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
         fn = getattr(lib, "allred_plan_adamw_all_gather_shards_" + fmt)
+        extra = () if sign_mask is None else (int(sign_mask) & 0xFFFFFFFF,)
         check(fn(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups), int(norm_sq_ptr or 0) or None,
-                 int(info_ptr or 0) or None, flags, _stream_ptr(stream)),
+                 int(info_ptr or 0) or None, flags, *extra, _stream_ptr(stream)),
               "plan_adamw_all_gather_shards_" + fmt)
 
     def adamw_shards_mxfp8_launches(self, buckets) -> int:
@@ -643,6 +681,14 @@ class Plan:
         if st < 0:
             raise AllredError(st, "plan_adamw_shards_mxfp4_launches")
         return st
+
+    def adamw_all_gather_shards_mxfp4_rht(self, buckets, group_of, hyper_ptr, ngroups: int, sign_mask: int, norm_sq_ptr=None,
+                                          info_ptr=None, zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp4_rht: adamw_all_gather_shards_mxfp4 — the same planes and info,
+        bit for bit — with the rows all_gather_shards_mxfp4_rht(sign_mask) writes from the new parameters: a copy
+        of p' is rotated in the registers it is computed in.  As many launches as adamw_shards_mxfp4_launches says."""
+        self._adamw_mx_run("mxfp4_rht", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream,
+                           sign_mask=sign_mask)
 
     @staticmethod
     def _adamw_mx2d_buckets_f32(buckets):

@@ -268,6 +268,7 @@ SIGNATURES = [
     ("allred_plan_all_gather_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp4", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
+    ("allred_plan_all_gather_shards_mxfp4_rht", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, C.c_uint32, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp4_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
@@ -278,6 +279,8 @@ SIGNATURES = [
     ("allred_plan_adamw_all_gather_shards_mxfp4", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
+    ("allred_plan_adamw_all_gather_shards_mxfp4_rht", C.c_int,
+     [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint32, _P]),
     ("allred_plan_adamw_all_gather_shards_mxfp8_2d", C.c_int,
      [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),

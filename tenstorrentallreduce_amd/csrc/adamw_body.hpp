@@ -1,7 +1,8 @@
 // adamw_body.hpp — the ONE AdamW body of the fp32-shard calls, adamw_ag, with its kernel-argument
 // tables: included by adamw_kernels.hip (k_adamw_ag_group_f32, k_adamw_ag_groups_f32: bf16 rank rows)
 // adamw_mx_kernels.hip (k_adamw_ag_mxfp8: MXFP8 element rows and E8M0 scale rows) and
-// adamw_mx4_kernels.hip (k_adamw_ag_mxfp4: MXFP4 nibble rows and E8M0 scale rows).  The output
+// adamw_mx4_kernels.hip (k_adamw_ag_mxfp4: MXFP4 nibble rows and E8M0 scale rows) and adamw_mx4_rht_kernels.hip
+// (k_adamw_ag_mxfp4_rht: the same rows from a ROTATED copy of p').  The output
 // stage — what wave 0 puts into the LDS slot for p' and what every wave stores from it — is a
 // compile-time choice (AdamwOut); everything else is the same code in every instance.
 #pragma once
@@ -11,6 +12,7 @@
 #include "device.hpp"
 #include "group_span.hpp"
 #include "mx_quant.hpp"
+#include "mx_rht.hpp"
 
 namespace tsa {
 namespace {
@@ -53,7 +55,9 @@ static_assert(sizeof(allred_adamw_hyper) == 32 && sizeof(allred_adamw_bucket_f32
 //   kOutMx4Floor MXFP4: 2 bytes of e2m1 nibbles per lane and the tile's 8 E8M0 bytes, a 144-byte slot,
 //   kOutMx4Rceil 8-byte row stores in k_ag_group_mxfp4's split (four rows per store instruction) and
 //                one 8-byte scale store per rank row.
-enum AdamwOut { kOutBf16 = 0, kOutMxFloor, kOutMxRceil, kOutMx4Floor, kOutMx4Rceil };
+//   kOutMx4RhtFloor  the MXFP4 stage on a copy of p' that went through the random Hadamard rotation of
+//   kOutMx4RhtRceil  mx_rht.hpp first; slot, barrier and stores are kOutMx4Floor's / kOutMx4Rceil's.
+enum AdamwOut { kOutBf16 = 0, kOutMxFloor, kOutMxRceil, kOutMx4Floor, kOutMx4Rceil, kOutMx4RhtFloor, kOutMx4RhtRceil };
 // The scale rows of every bucket of an MXFP8 launch: rank r's scale row at scales + r * scale_stride
 // bytes.  GroupSpan then carries the ELEMENT rows in bytes (GroupBucket::ranks row 0, ::stride the
 // row stride in bytes), as in mx_kernels.hip; the MXFP4 stage takes the same table.  The bf16 kernels
@@ -90,6 +94,14 @@ template <>
 struct AdamwSlot<kOutMx4Rceil> {
     typedef uint32_t type[2][36];
 };
+template <>
+struct AdamwSlot<kOutMx4RhtFloor> {
+    typedef uint32_t type[2][36];
+};
+template <>
+struct AdamwSlot<kOutMx4RhtRceil> {
+    typedef uint32_t type[2][36];
+};
 
 // the value lane `g` of this wave holds in x, as a wave-uniform (scalar) value; g is wave-uniform
 __device__ __forceinline__ float from_lane(float x, int g) {
@@ -108,7 +120,7 @@ struct PerGroup {
     float beta1, beta2, eps, bc2;
 };
 
-// Wave 0, all 64 lanes active.  max_norm: the one set's, or hyper[0]'s, wave-uniform; x =
+// Wave 0, all 64 lanes active.  max_norm: the one set's, or hypey.p[0]'s, wave-uniform; x =
 // norm_sq[lane] (lane < P, else +0.0f; given: norm_sq != NULL).
 __device__ __forceinline__ CallWide call_wide(float max_norm, float x, bool given) {
     CallWide u{0.0f, 1.0f, false};
@@ -204,14 +216,32 @@ __device__ __forceinline__ PerGroup per_group(const allred_adamw_hyper& h) {
 //   scalar branch).  The one early return stays the workgroup-uniform `mine <= 0`.  The slot-rotation
 //   argument above therefore carries over unchanged: a wave without rows has no LDS read to protect,
 //   and a wave with rows has passed the barrier of tile j + 1 behind its read of tile j as before.
+// OUT == kOutMx4RhtFloor / kOutMx4RhtRceil: allred.h's rotation (mx_rht.hpp) on a COPY of p' in wave 0's
+// registers, in front of the MXFP4 stage above, which then takes the copy; y.p, and with it the param plane,
+// is untouched.  Lane l holds elements 4 (l & 7) .. 4 (l & 7) + 3 of its eight-lane block:
+//   signs   four v_xor_b32 with the lane's masks (bits 4 (l & 7) .. + 3 of sign_mask at bit 31: four
+//           registers filled once, in front of the tile loop);
+//   h = 1, 2   eight v_add_f32 / v_sub_f32 on the lane's own four registers;
+//   h = 4   lane ^ 1, quad_perm [1, 0, 3, 2];   h = 8   lane ^ 2, quad_perm [2, 3, 0, 1]: per register one
+//           v_add_f32 with a DPP operand, own's sign flipped where the lane holds the upper half of the pair;
+//   h = 16  lane ^ 4.  gfx9 DPP has no xor form for it: row_half_mirror (lane 7 - i of the eight) composed
+//           with quad_perm [3, 2, 1, 0] (lane 3 - i of the quad) is i ^ 7 ^ 3 = i ^ 4 — a v_mov_b32 with DPP
+//           and the v_add_f32 with DPP, eight VALU operations for the four registers.  ds_swizzle_b32 and
+//           ds_bpermute_b32 do it in one operation each, but through the LDS queue: their results would be
+//           waited for with lgkmcnt next to the slot writes and the scalar loads of the walk, in a wave that is
+//           the workgroup's critical path in front of the barrier; the DPP pair stays in the VALU.
+//   2^-2.5  four v_mul_f32.
+// The stages and operands are in the rule's order, so the bits are k_ag_group_mxfp4_rht's.
 // ---------------------------------------------------------------------------
 template <int P, bool ZERO, bool GROUPS, AdamwOut OUT = kOutBf16, class Scales = AdamwNoScales>
 __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup& planes, const AdamwGroupOf& group_of,
                                          const allred_adamw_hyper* __restrict__ hyper, int ngroups,
-                                         const float* __restrict__ norm_sq, float* info, const Scales& scale_rows = Scales{}) {
-    constexpr bool MX4 = OUT == kOutMx4Floor || OUT == kOutMx4Rceil;
+                                         const float* __restrict__ norm_sq, float* info, const Scales& scale_rows = Scales{},
+                                         uint32_t sign_mask = 0) {
+    constexpr bool RHT = OUT == kOutMx4RhtFloor || OUT == kOutMx4RhtRceil;   // the rotation in front of the MXFP4 stage
+    constexpr bool MX4 = OUT == kOutMx4Floor || OUT == kOutMx4Rceil || RHT;
     constexpr bool MX = OUT != kOutBf16;   // any MX row format: element rows in bytes, and scale rows
-    constexpr bool RCEIL = OUT == kOutMxRceil || OUT == kOutMx4Rceil;
+    constexpr bool RCEIL = OUT == kOutMxRceil || OUT == kOutMx4Rceil || OUT == kOutMx4RhtRceil;
     // TV: lanes of a row's run; RPI: rows per store instruction; W: waves with rows (MX4 at P = 8: two)
     constexpr int TV = MX4 ? 16 : 32, RPI = 64 / TV, W = (MX4 && P / RPI < 4) ? P / RPI : 4, RPW = P / W, OPS = RPW / RPI;
     constexpr int SC = MX4 ? 32 : 64;   // the slot's dword that holds the tile's scale bytes
@@ -220,6 +250,9 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
     __shared__ __attribute__((aligned(16))) typename AdamwSlot<OUT>::type slot;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane % TV, q = lane / TV;
+    // RHT only; filled under if constexpr: computed in every form, and dead there, it moved the MX forms' registers
+    RhtLane<4> rl;
+    if constexpr (RHT) rl = rht_lane<4>(sign_mask, lane & 7);
     struct Tile {
         uint16_t* ranks;   // the bucket's row 0
         uint64_t stride;
@@ -353,6 +386,22 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
             }
         }
         if constexpr (MX) {
+            // RHT: the stage below quantises y.p, so the rotated values stand in y.p while it runs and p' is put
+            // back behind it (register renaming, no instruction); written this way the other forms' code, and
+            // with it their ISA, is untouched — with a named copy in front of the stage their registers moved
+            f32x4 unrotated{};
+            if constexpr (RHT) {
+                unrotated = y.p;
+                float x[4] = {y.p[0], y.p[1], y.p[2], y.p[3]};
+                rht_own(x, rl);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    x[e] = rht_pair(dpp_f<0xB1>(x[e]), x[e], rl.upper[0]);                  // h = 4: lane ^ 1
+                    x[e] = rht_pair(dpp_f<0x4E>(x[e]), x[e], rl.upper[1]);                  // h = 8: lane ^ 2
+                    x[e] = rht_pair(dpp_f<0x1B>(dpp_f<0x141>(x[e])), x[e], rl.upper[2]);    // h = 16: lane ^ 4
+                    y.p[e] = rht_norm(x[e]);
+                }
+            }
             uint32_t A = umax(umax(abs_bits(y.p[0]), abs_bits(y.p[1])), umax(abs_bits(y.p[2]), abs_bits(y.p[3])));
             A = max_dpp<0xB1>(A);    // quad_perm [1, 0, 3, 2]: lane ^ 1
             A = max_dpp<0x4E>(A);    // quad_perm [2, 3, 0, 1]: lane ^ 2
@@ -372,6 +421,7 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
                 slot[j & 1][lane] = special ? 0x7f7f7f7fu : e;
             }
             if ((lane & 7) == 0) reinterpret_cast<uint8_t*>(&slot[j & 1][SC])[lane >> 3] = (uint8_t)(special ? 0xffu : (uint32_t)sb);
+            if constexpr (RHT) y.p = unrotated;
         } else {
             slot[j & 1][lane] = make_uint2(pack_rne(y.p[0], y.p[1]), pack_rne(y.p[2], y.p[3]));
         }

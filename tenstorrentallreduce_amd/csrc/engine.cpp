@@ -1170,6 +1170,16 @@ int allred_plan_all_gather_shards_mxfp4_launches(const allred_plan* p, const all
     return launch_ag_group_mxfp4(buckets, count, p->total, false, /*dry=*/true, nullptr);
 }
 
+// allred_plan_all_gather_shards_mxfp4's checks and flags; any sign_mask is valid
+int allred_plan_all_gather_shards_mxfp4_rht(allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                            uint32_t sign_mask, void* stream) {
+    const int st = mx_check(p, buckets, count, flags, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp4_rht(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, sign_mask, stream);
+}
+
 int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,
                                            void* stream) {
     const int st = mx2d_check(p, buckets, count, flags);
@@ -1321,6 +1331,21 @@ int allred_plan_adamw_shards_mxfp4_launches(const allred_plan* p, const allred_a
     if (st != ALLRED_OK || count == 0) return st;
     return launch_adamw_group_mxfp4(buckets, nullptr, count, p->total, nullptr, /*ngroups=*/1, nullptr, nullptr, false, false,
                                     /*dry=*/true, nullptr);
+}
+
+// allred_plan_adamw_all_gather_shards_mxfp4's checks and flags, all of it before any HIP call; any sign_mask is valid
+int allred_plan_adamw_all_gather_shards_mxfp4_rht(allred_plan* p, const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of,
+                                                  int count, const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq,
+                                                  float* info, int flags, uint32_t sign_mask, void* stream) {
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_mx_check(p, buckets, count, hyper, norm_sq, info, flags, /*dry=*/false,
+                                  kAdamwHyperBytes * (uint64_t)ngroups, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_mxfp4_rht(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                        (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0, sign_mask,
+                                        stream);
 }
 
 // The group rules first, then adamw_mx2d_check with the whole hyper array as hyper's interval; all of it

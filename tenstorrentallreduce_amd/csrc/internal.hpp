@@ -130,6 +130,10 @@ int launch_ag_group_mxfp8(const allred_mx_bucket_f32* buckets, int count, int to
 // The same list through allred_plan_all_gather_shards_mxfp4 (mx4_kernels.hip): the shard quantised to
 // MXFP4, two e2m1 elements per row byte — k_ag_group_mxfp4 —, ALLRED_MX_GROUP_MAX buckets per launch.
 int launch_ag_group_mxfp4(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+// The same list through allred_plan_all_gather_shards_mxfp4_rht (mx4_rht_kernels.hip): every MX block rotated
+// (sign_mask, then the 32-point Hadamard transform) in front of the MXFP4 quantiser — k_ag_group_mxfp4_rht —,
+// batched as launch_ag_group_mxfp4 batches; no dry form: that call's launch count holds.
+int launch_ag_group_mxfp4_rht(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, uint32_t sign_mask, void* stream);
 // a list of (checked) buckets of one fp32 matrix each (mx2d_kernels.hip): the shard quantised to MXFP8
 // both row-wise (where a bucket has rows) and column-wise, as W^T, into every rank's rows —
 // k_ag_group_mxfp8_2d —, ALLRED_MX2D_GROUP_MAX buckets per launch.  rceil, dry: as above.
@@ -149,6 +153,12 @@ int launch_adamw_group_mxfp8(const allred_adamw_mx_bucket_f32* buckets, const ui
 int launch_adamw_group_mxfp4(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                              const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                              bool rceil, bool dry, void* stream);
+// The same list through allred_plan_adamw_all_gather_shards_mxfp4_rht (adamw_mx4_rht_kernels.hip): the same
+// update, a rotated copy of p' quantised to MXFP4 — k_adamw_ag_mxfp4_rht —, batched as launch_adamw_group_mxfp4
+// batches; no dry form: that call's launch count holds.
+int launch_adamw_group_mxfp4_rht(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                                 const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                                 bool rceil, uint32_t sign_mask, void* stream);
 // a list of (checked) buckets of one fp32 matrix each, held as four planes (adamw_mx2d_kernels.hip):
 // launch_adamw_group_mxfp8's update, p' quantised to MXFP8 both row-wise (where a bucket has rows) and
 // column-wise into every rank's rows — k_adamw_ag_mxfp8_2d —, ALLRED_ADAMW_MX2D_GROUP_MAX buckets per launch.
