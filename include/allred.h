@@ -73,6 +73,9 @@ extern "C" {
  * orientations of p', each rounded once from fp32, on allred_adamw_mx2d_bucket_f32's list.
  * Still ABI 7: allred_plan_all_gather_shards_mxfp4_rht and allred_plan_adamw_all_gather_shards_mxfp4_rht are
  * additions — the two 1D MXFP4 calls with a random Hadamard rotation of every MX block in front of the quantiser.
+ * Still ABI 7: allred_mx_sr_state, ALLRED_MX_SR_ROTATE, ALLRED_ADAMW_MX_ROTATE, allred_plan_all_gather_shards_mxfp4_sr
+ * and allred_plan_adamw_all_gather_shards_mxfp4_sr are additions — the two 1D MXFP4 calls with stochastic rounding
+ * onto the e2m1 grid (Philox4x32-10, the seed and step in device memory), rotated or not.
  * Still ABI 7: allred_launch_rec and allred_launch_trace_begin / allred_launch_trace_end are
  * additions — the ordered list of the kernels a thread launched; allred_last_launch is unchanged. */
 #define ALLRED_ABI_VERSION 7
@@ -805,6 +808,53 @@ int allred_plan_all_gather_shards_mxfp4_launches(const allred_plan* plan, const 
  * No matrix instruction computes this: the order of the additions is part of the contract. */
 int allred_plan_all_gather_shards_mxfp4_rht(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
                                             uint32_t sign_mask, void* stream);
+/* MXFP4 ALL-GATHER WITH STOCHASTIC ROUNDING: allred_plan_all_gather_shards_mxfp4 with the last step — y_i onto
+ * the e2m1 grid — rounded STOCHASTICALLY instead of to nearest even, as the published MXFP4 training recipes
+ * round the operand of the backward GEMM: RNE on 3-bit magnitudes is biased per element and the bias does not
+ * average out over a contraction; SR is unbiased.  With ALLRED_MX_SR_ROTATE the rotation of
+ * allred_plan_all_gather_shards_mxfp4_rht runs first (the signs, the five stages in order, one multiply by
+ * 0x3E3504F3); without it sign_mask is ignored.  The kernel writes ONE quantisation to all P rank rows, so
+ * every rank holds the same bits with no RNG kept in step between ranks.  The bucket list, the accepted plans,
+ * the checks, the rows, the plain-linear scale rows, the nibble order, count == 0 and the batching (32 buckets
+ * per launch in list order) are allred_plan_all_gather_shards_mxfp4's.  flags: ALLRED_MX_SCALE_RCEIL (bit 0)
+ * and ALLRED_MX_SR_ROTATE (bit 1); the older calls keep refusing bit 1.  The kernel traces as
+ * k_ag_group_mxfp4_sr<P, false|true, false|true> (csrc/mx4_sr_kernels.hip; the bools: RCEIL, ROTATE).  No
+ * reference counterpart, no tune key, no _launches twin: the call enqueues what
+ * allred_plan_all_gather_shards_mxfp4_launches returns for the same list; pipe_grid caps the grid.
+ * THE STATE: 16 bytes of DEVICE memory, 8-byte aligned, only read — by a wave-uniform load inside the kernel,
+ * so a call captured into a graph ONCE takes fresh randomness on every replay: the user bumps `step` in device
+ * memory between replays.  `reserved` is ignored.  CHECKS on sr, before any HIP call (a refused call writes
+ * nothing): ALLRED_ERR_ARG for NULL or (uintptr_t)sr % 8 != 0, and for the WHOLE list if [sr, sr + 16) shares
+ * a byte with any element row interval or scale row interval (csrc/mx_ranges.hpp mx_small_disjoint).
+ * THE SR RULE binds every implementation bit for bit.  Per MX block of 32 values (rotated if asked): A, the
+ * NaN/Inf block (scale 0xFF over sixteen 0x00 bytes), X, the scale byte and y_i = x_i * 2^(-X) are EXACTLY the
+ * MXFP4 call's.  Then, with a = bits(y_i) & 0x7fffffff and r = w_i & 0x3fffff (w_i below):
+ *   a >= 0x3f800000 (|y| >= 1; |y| < 8 always holds):  q = (a + r) & ~0x3fffff,
+ *       code = min((q >> 22) - 0xFC, 7): 1, 1.5, 2, 3, 4, 6 are codes 2 .. 7, a carry to 8 saturates to 6;
+ *   otherwise:  E = a >> 23,  T = E >= 104 ? ((a & 0x7fffff) | 0x800000) >> (127 - E) : 0
+ *       (= floor(|y| * 2^23); fp32 denormals give 0),  code = (T + r) >> 22: 0, 0.5 or 1.
+ *   Bit 3 is the sign of y_i, always kept, as in the RNE call.
+ * A value ON the e2m1 grid never moves; otherwise the probability of rounding away from zero is the dropped
+ * fraction, to 2^-22, and r = 0 truncates toward zero.  Under ALLRED_MX_SCALE_RCEIL |y| <= 6: nothing saturates
+ * and the rounding is unbiased.  Under the FLOOR rule scaled values in (6, 8) exist and still saturate to 6:
+ * those elements keep a bias toward zero.
+ * w_i is output word (e % 4) of Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9,
+ * 0xBB67AE85) with
+ *   key      (seed & 0xffffffff, seed >> 32)
+ *   counter  (g & 0xffffffff, g >> 32, the bucket's index in the CALLER's list, step),  g = e / 4,
+ * e the element's position in the gathered row, 0 .. elems_per_rank - 1 — with rotation the position of the
+ * rotated output.  The bits therefore depend on neither P, the launch batching nor the grid.  Known answers
+ * (counter / key / output): 0,0,0,0 / 0,0 / 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all-ones / all-ones /
+ * 408f276d 41c83b0e a20bc7c6 6d5451fd; 243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 /
+ * d16cfe09 94fdcceb 5001e420 24126ea1. */
+#define ALLRED_MX_SR_ROTATE 2           /* flags bit 1 of allred_plan_all_gather_shards_mxfp4_sr; bit 0 stays ALLRED_MX_SCALE_RCEIL */
+typedef struct {                        /* 16 bytes, lives in DEVICE memory, 8-byte aligned, only read */
+    uint64_t seed;
+    uint32_t step;
+    uint32_t reserved;
+} allred_mx_sr_state;
+int allred_plan_all_gather_shards_mxfp4_sr(allred_plan* plan, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                           uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream);
 /* BOTH MXFP8 ORIENTATIONS FROM ONE PASS: allred_plan_all_gather_shards_mxfp8 for a weight that is used in
  * two GEMMs.  An MX block runs along the contraction dimension: Y = X W^T contracts over `in`, the columns
  * of W[out][in], and takes the rows above; the input-gradient GEMM dX = dY W contracts over `out` and
@@ -1050,6 +1100,28 @@ int allred_plan_adamw_all_gather_shards_mxfp4_rht(
     const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
     const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
     int flags, uint32_t sign_mask, void* stream);
+/* ADAMW INSIDE THE STOCHASTICALLY ROUNDED MXFP4 ALL-GATHER: allred_plan_adamw_all_gather_shards_mxfp4 with the
+ * rows of allred_plan_all_gather_shards_mxfp4_sr.  Every argument, check and status is that of
+ * allred_plan_adamw_all_gather_shards_mxfp4_rht; sr (that call's rules, and [sr, sr + 16) must share no byte
+ * with a row, a scale row, a plane block or info: csrc/adamw_mx_ranges.hpp adamw_mx_small_disjoint) stands in
+ * front of stream.  flags: ALLRED_ADAMW_ZERO_GRAD (bit 0), ALLRED_ADAMW_MX_RCEIL (bit 1) and
+ * ALLRED_ADAMW_MX_ROTATE (bit 2: the rotation first; without it sign_mask is ignored); the older calls keep
+ * refusing bit 2.  The kernel traces as k_adamw_ag_mxfp4_sr<P, false|true, false|true, false|true>
+ * (csrc/adamw_mx4_sr_kernels.hip; the bools: ZERO_GRAD, RCEIL, ROTATE).
+ * GUARANTEE (tests/test_gpu_adamw_mx4_sr.py): the four planes and info come out bit for bit as
+ * allred_plan_adamw_all_gather_shards_mxfp4 — the UNROTATED RNE call — leaves them, and the element rows and
+ * scale rows bit for bit as allred_plan_all_gather_shards_mxfp4_sr (same scale rule, rotate bit, sign_mask and
+ * state, the same place in the list) writes them from the param plane this call leaves: p', or p on a skipped
+ * step.
+ * LAUNCHES: no _launches twin; the call enqueues what allred_plan_adamw_shards_mxfp4_launches returns for the
+ * same list, with 3936 bytes of kernel arguments, and can be captured into a graph. */
+#define ALLRED_ADAMW_MX_ROTATE 4         /* flags bit 2 of allred_plan_adamw_all_gather_shards_mxfp4_sr */
+int allred_plan_adamw_all_gather_shards_mxfp4_sr(
+    allred_plan* plan, const allred_adamw_mx_bucket_f32* buckets,
+    const uint8_t* group_of /* [count], HOST; NULL: every bucket in group 0 */, int count,
+    const allred_adamw_hyper* hyper /* DEVICE, [ngroups] x 32 bytes, 16-byte aligned, only read */, int ngroups,
+    const float* norm_sq /* [total], device, or NULL */, float* info /* [4], device, or NULL */,
+    int flags, uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream);
 /* ADAMW INSIDE THE 2D MXFP8 ALL-GATHER: the call above with the outputs of
  * allred_plan_all_gather_shards_mxfp8_2d — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call) with BOTH GEMM operands, the row-wise rows

@@ -34,7 +34,7 @@ __all__ = [
     "MULTI_HIER", "MULTI_LOCAL", "validate_device", "dist_reduce_scatter", "dist_all_gather",
     "dist_reduce_scatter_host", "dist_all_gather_host", "OP_REDUCE_SCATTER", "OP_ALL_GATHER",
     "adamw_hyper", "adamw_hyper_groups", "ADAMW_PARAM_GROUPS_MAX", "mxfp8_dequantize", "mxfp4_dequantize",
-    "hadamard32",
+    "hadamard32", "philox4x32_10", "e2m1_sr", "mxfp4_sr_quantize",
 ]
 
 
@@ -272,6 +272,65 @@ def hadamard32(x, sign_mask: int, inverse: bool = False) -> np.ndarray:
     if inverse:
         v = (v.view(np.uint32) ^ signs).view(np.float32)
     return v.reshape(x.shape)
+
+
+def philox4x32_10(counter, key) -> np.ndarray:
+    """Philox4x32-10 (Salmon et al., SC'11) in numpy integers: counter (..., 4) and key (..., 2) words below
+    2^32, broadcast against each other; the four output words as uint32 (..., 4).  The generator of
+    Plan.all_gather_shards_mxfp4_sr (allred.h has three known answers)."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    if c.shape[-1] != 4 or k.shape[-1] != 2:
+        raise ValueError(f"a counter is four words and a key two, not {c.shape} and {k.shape}")
+    lo = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (c[..., i] for i in range(4))
+    k0, k1 = k[..., 0], k[..., 1]
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2   # 32 x 32 bits: no wrap in 64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & lo, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & lo
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & lo, (k1 + np.uint64(0xBB67AE85)) & lo
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def e2m1_sr(y, words) -> np.ndarray:
+    """allred.h's SR rule for scaled values: float32 y with |y| < 8 and one 32-bit word each (the low 22 bits
+    count) -> the e2m1 nibble as uint8, bit 3 the sign.  At or above 1 the word is added to the float's bits below
+    the kept mantissa bit; below 1 to floor(|y| 2^23), the grid 0, 0.5, 1 being uniform there."""
+    bits = np.ascontiguousarray(y, dtype=np.float32).view(np.uint32)
+    a, r = bits & np.uint32(0x7FFFFFFF), np.asarray(words, dtype=np.uint32) & np.uint32(0x3FFFFF)
+    big = np.minimum(((a + r) >> np.uint32(22)).astype(np.int64) - 0xFC, 7)
+    e = a >> np.uint32(23)
+    t = np.where(e >= 104, ((a & np.uint32(0x7FFFFF)) | np.uint32(0x800000)) >> np.clip(127 - e.astype(np.int64), 0, 31).astype(np.uint32), 0)
+    small = (t.astype(np.uint32) + r) >> np.uint32(22)
+    return (np.where(a >= 0x3F800000, big, small) | ((bits >> np.uint32(28)) & np.uint32(8))).astype(np.uint8)
+
+
+def mxfp4_sr_quantize(x, seed: int, step: int, bucket: int, rceil: bool = False, sign_mask=None):
+    """Plan.all_gather_shards_mxfp4_sr on the host, integer for integer: x (..., n) float32, the last axis a
+    GATHERED ROW (element e at index e; n % 32 == 0), quantised as bucket number `bucket` of the caller's list
+    under the state (seed, step) -> (bytes (..., n / 2) uint8, scales (..., n / 32) uint8).  sign_mask: None, or
+    hadamard32's rotation first.  Amax, scale byte (floor rule, or rceil) and the one multiply by 2^-X are the
+    MXFP4 call's; the word of element e is word e % 4 of philox4x32_10((e / 4, 0 .. , bucket, step), seed)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n = x.shape[-1]
+    if n % 32:
+        raise ValueError(f"the last axis of {x.shape} is no multiple of 32")
+    if sign_mask is not None:
+        x = hadamard32(x, sign_mask)
+    amax = (x.view(np.uint32) & np.uint32(0x7FFFFFFF)).reshape(x.shape[:-1] + (n // 32, 32)).max(axis=-1)
+    special = amax >= 0x7F800000
+    sb = (amax >> np.uint32(23)).astype(np.int64) - 2
+    if rceil:
+        sb += (amax & np.uint32(0x7FFFFF)) > 0x400000
+    sb = np.maximum(sb, 0)
+    inv = (np.maximum(254 - sb, 0).astype(np.uint32) << np.uint32(23)).view(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = x * np.repeat(inv, 32, axis=-1)
+    g = np.arange(n // 4, dtype=np.uint64)
+    counter = np.stack([g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), np.full_like(g, int(bucket)), np.full_like(g, int(step))], axis=-1)
+    words = philox4x32_10(counter, [int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF]).reshape(n)
+    code = np.where(np.repeat(special, 32, axis=-1), 0, e2m1_sr(y, words)).astype(np.uint8)
+    return code[..., 0::2] | (code[..., 1::2] << np.uint8(4)), np.where(special, 0xFF, sb).astype(np.uint8)
 
 
 # ---------------------------------------------------------------- device
@@ -572,6 +631,19 @@ class Plan:
         check(lib.allred_plan_all_gather_shards_mxfp4_rht(self._h, arr, count, flags, int(sign_mask) & 0xFFFFFFFF, _stream_ptr(stream)),
               "plan_all_gather_shards_mxfp4_rht")
 
+    def all_gather_shards_mxfp4_sr(self, buckets, sr_ptr, sign_mask=None, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp4_sr: all_gather_shards_mxfp4 with STOCHASTIC rounding onto the e2m1
+        grid — unbiased (under rceil; the floor rule still saturates scaled values in (6, 8)), the same bits in
+        every rank's rows.  sr_ptr: 16 bytes of DEVICE memory, 8-byte aligned — uint64 seed, uint32 step, uint32
+        reserved —, read by the kernel: a captured call takes fresh randomness on every replay once `step` is
+        rewritten there.  sign_mask: None for no rotation, else all_gather_shards_mxfp4_rht's rotation first.
+        mxfp4_sr_quantize is the same rule on the host.  As many launches as shards_mxfp4_launches says."""
+        arr, count = self._mx_buckets_f32(buckets)
+        flags = (_lib.MX_SCALE_RCEIL if rceil else 0) | (0 if sign_mask is None else _lib.MX_SR_ROTATE)
+        check(lib.allred_plan_all_gather_shards_mxfp4_sr(self._h, arr, count, flags, int(sign_mask or 0) & 0xFFFFFFFF,
+                                                         int(sr_ptr or 0) or None, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp4_sr")
+
     @staticmethod
     def _mx2d_buckets_f32(buckets):
         """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, t_rows_ptr, t_row_stride, t_scales_ptr,
@@ -638,9 +710,9 @@ class Plan:
         self._adamw_mx_run("mxfp8", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream)
 
     def _adamw_mx_run(self, fmt, buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream,
-                      sign_mask=None):
+                      sign_mask=None, sr_ptr=None, extra_flags=0):
         """allred_plan_adamw_all_gather_shards_<fmt>: the MXFP8 and the MXFP4 call take the same arguments, the
-        rotated MXFP4 call sign_mask in front of the stream"""
+        rotated MXFP4 call sign_mask in front of the stream, the SR call sign_mask and sr"""
         arr, count = self._adamw_mx_buckets_f32(buckets)
         groups = None
         if group_of is not None:
@@ -649,9 +721,11 @@ class Plan:
             if any(not 0 <= int(g) <= 255 for g in group_of):
                 raise ValueError("a group index is one byte")
             groups = (C.c_uint8 * max(count, 1))(*[int(g) for g in group_of])
-        flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0)
+        flags = (_lib.ADAMW_ZERO_GRAD if zero_grad else 0) | (_lib.ADAMW_MX_RCEIL if rceil else 0) | extra_flags
         fn = getattr(lib, "allred_plan_adamw_all_gather_shards_" + fmt)
         extra = () if sign_mask is None else (int(sign_mask) & 0xFFFFFFFF,)
+        if fmt == "mxfp4_sr":
+            extra += (int(sr_ptr or 0) or None,)
         check(fn(self._h, arr, groups, count, int(hyper_ptr) or None, int(ngroups), int(norm_sq_ptr or 0) or None,
                  int(info_ptr or 0) or None, flags, *extra, _stream_ptr(stream)),
               "plan_adamw_all_gather_shards_" + fmt)
@@ -689,6 +763,14 @@ class Plan:
         of p' is rotated in the registers it is computed in.  As many launches as adamw_shards_mxfp4_launches says."""
         self._adamw_mx_run("mxfp4_rht", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream,
                            sign_mask=sign_mask)
+
+    def adamw_all_gather_shards_mxfp4_sr(self, buckets, group_of, hyper_ptr, ngroups: int, sr_ptr, sign_mask=None, norm_sq_ptr=None,
+                                         info_ptr=None, zero_grad: bool = False, rceil: bool = False, stream=None) -> None:
+        """allred_plan_adamw_all_gather_shards_mxfp4_sr: adamw_all_gather_shards_mxfp4 — the same planes and info,
+        bit for bit — with the rows all_gather_shards_mxfp4_sr(sr_ptr, sign_mask) writes from the new parameters
+        (p on a skipped step).  sr_ptr and sign_mask: as there.  As many launches as adamw_shards_mxfp4_launches says."""
+        self._adamw_mx_run("mxfp4_sr", buckets, group_of, hyper_ptr, ngroups, norm_sq_ptr, info_ptr, zero_grad, rceil, stream,
+                           sign_mask=sign_mask or 0, sr_ptr=sr_ptr, extra_flags=0 if sign_mask is None else _lib.ADAMW_MX_ROTATE)
 
     @staticmethod
     def _adamw_mx2d_buckets_f32(buckets):

@@ -170,6 +170,7 @@ class MxBucketF32(C.Structure):   # allred_mx_bucket_f32: e4m3 element rows, E8M
 
 MX_GROUP_MAX = 32     # ALLRED_MX_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8 covers
 MX_SCALE_RCEIL = 1    # ALLRED_MX_SCALE_RCEIL: its flags bit 0
+MX_SR_ROTATE = 2      # ALLRED_MX_SR_ROTATE: flags bit 1 of allred_plan_all_gather_shards_mxfp4_sr alone
 
 
 class Mx2dBucketF32(C.Structure):   # allred_mx2d_bucket_f32: MxBucketF32's rows and scales (both may be NULL), the rows of W^T, the matrix
@@ -191,6 +192,7 @@ class AdamwMxBucketF32(C.Structure):   # allred_adamw_mx_bucket_f32: MxBucketF32
 
 ADAMW_MX_GROUP_MAX = 32   # ALLRED_ADAMW_MX_GROUP_MAX: buckets one launch of allred_plan_adamw_all_gather_shards_mxfp8 covers
 ADAMW_MX_RCEIL = 2        # ALLRED_ADAMW_MX_RCEIL: its flags bit 1 (bit 0: ADAMW_ZERO_GRAD)
+ADAMW_MX_ROTATE = 4       # ALLRED_ADAMW_MX_ROTATE: flags bit 2 of allred_plan_adamw_all_gather_shards_mxfp4_sr alone
 
 
 class AdamwMx2dBucketF32(C.Structure):   # allred_adamw_mx2d_bucket_f32: Mx2dBucketF32's outputs and matrix, AdamwBucketF32's four planes
@@ -269,6 +271,7 @@ SIGNATURES = [
     ("allred_plan_all_gather_shards_mxfp4", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp4_rht", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, C.c_uint32, _P]),
+    ("allred_plan_all_gather_shards_mxfp4_sr", C.c_int, [_P, C.POINTER(MxBucketF32), C.c_int, C.c_int, C.c_uint32, _P, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp4_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
@@ -281,6 +284,8 @@ SIGNATURES = [
     ("allred_plan_adamw_shards_mxfp4_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp4_rht", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint32, _P]),
+    ("allred_plan_adamw_all_gather_shards_mxfp4_sr", C.c_int,
+     [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint32, _P, _P]),
     ("allred_plan_adamw_all_gather_shards_mxfp8_2d", C.c_int,
      [_P, C.POINTER(AdamwMx2dBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(AdamwMx2dBucketF32), C.c_int]),

@@ -2,7 +2,8 @@
 // tables: included by adamw_kernels.hip (k_adamw_ag_group_f32, k_adamw_ag_groups_f32: bf16 rank rows)
 // adamw_mx_kernels.hip (k_adamw_ag_mxfp8: MXFP8 element rows and E8M0 scale rows) and
 // adamw_mx4_kernels.hip (k_adamw_ag_mxfp4: MXFP4 nibble rows and E8M0 scale rows) and adamw_mx4_rht_kernels.hip
-// (k_adamw_ag_mxfp4_rht: the same rows from a ROTATED copy of p').  The output
+// (k_adamw_ag_mxfp4_rht: the same rows from a ROTATED copy of p') and adamw_mx4_sr_kernels.hip
+// (k_adamw_ag_mxfp4_sr: the same rows rounded STOCHASTICALLY, rotated or not).  The output
 // stage — what wave 0 puts into the LDS slot for p' and what every wave stores from it — is a
 // compile-time choice (AdamwOut); everything else is the same code in every instance.
 #pragma once
@@ -13,6 +14,7 @@
 #include "group_span.hpp"
 #include "mx_quant.hpp"
 #include "mx_rht.hpp"
+#include "mx_sr.hpp"
 
 namespace tsa {
 namespace {
@@ -57,7 +59,13 @@ static_assert(sizeof(allred_adamw_hyper) == 32 && sizeof(allred_adamw_bucket_f32
 //                one 8-byte scale store per rank row.
 //   kOutMx4RhtFloor  the MXFP4 stage on a copy of p' that went through the random Hadamard rotation of
 //   kOutMx4RhtRceil  mx_rht.hpp first; slot, barrier and stores are kOutMx4Floor's / kOutMx4Rceil's.
-enum AdamwOut { kOutBf16 = 0, kOutMxFloor, kOutMxRceil, kOutMx4Floor, kOutMx4Rceil, kOutMx4RhtFloor, kOutMx4RhtRceil };
+//   kOutMx4SrFloor / kOutMx4SrRceil        the MXFP4 stage with mx_sr.hpp's stochastic rounding in place of the
+//   kOutMx4SrRhtFloor / kOutMx4SrRhtRceil  RNE conversion, on p' or on its rotated copy; slot, barrier and stores
+//                                          are kOutMx4Floor's / kOutMx4Rceil's.
+enum AdamwOut {
+    kOutBf16 = 0, kOutMxFloor, kOutMxRceil, kOutMx4Floor, kOutMx4Rceil, kOutMx4RhtFloor, kOutMx4RhtRceil,
+    kOutMx4SrFloor, kOutMx4SrRceil, kOutMx4SrRhtFloor, kOutMx4SrRhtRceil
+};
 // The scale rows of every bucket of an MXFP8 launch: rank r's scale row at scales + r * scale_stride
 // bytes.  GroupSpan then carries the ELEMENT rows in bytes (GroupBucket::ranks row 0, ::stride the
 // row stride in bytes), as in mx_kernels.hip; the MXFP4 stage takes the same table.  The bf16 kernels
@@ -102,6 +110,14 @@ template <>
 struct AdamwSlot<kOutMx4RhtRceil> {
     typedef uint32_t type[2][36];
 };
+template <>
+struct AdamwSlot<kOutMx4SrFloor> : AdamwSlot<kOutMx4Floor> {};
+template <>
+struct AdamwSlot<kOutMx4SrRceil> : AdamwSlot<kOutMx4Floor> {};
+template <>
+struct AdamwSlot<kOutMx4SrRhtFloor> : AdamwSlot<kOutMx4Floor> {};
+template <>
+struct AdamwSlot<kOutMx4SrRhtRceil> : AdamwSlot<kOutMx4Floor> {};
 
 // the value lane `g` of this wave holds in x, as a wave-uniform (scalar) value; g is wave-uniform
 __device__ __forceinline__ float from_lane(float x, int g) {
@@ -232,16 +248,28 @@ __device__ __forceinline__ PerGroup per_group(const allred_adamw_hyper& h) {
 //           the workgroup's critical path in front of the barrier; the DPP pair stays in the VALU.
 //   2^-2.5  four v_mul_f32.
 // The stages and operands are in the rule's order, so the bits are k_ag_group_mxfp4_rht's.
+// OUT == kOutMx4Sr*: allred.h's stochastic rounding (mx_sr.hpp) in place of the RNE conversion, behind the
+// rotation where the mode has one.  Wave 0's lane l holds elements 4 l .. 4 l + 3 of the tile, elements
+// 256 tile + 4 l .. of the gathered row: ONE Philox call, counter g = 64 tile + l, the bucket's index in the
+// caller's list (first_bucket + its index in the launch) and the step; the key and the step are read from sr
+// once, in front of the tile loop.  The words depend on indices alone: they are generated behind the issue of
+// the NEXT tile's loads and in front of the first use of this tile's planes (two sched_barriers hold them
+// there), about 85 integer operations under the loads' round trip.  On a skipped step y.p is p and the rows
+// are its SR quantisation.
 // ---------------------------------------------------------------------------
 template <int P, bool ZERO, bool GROUPS, AdamwOut OUT = kOutBf16, class Scales = AdamwNoScales>
 __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup& planes, const AdamwGroupOf& group_of,
                                          const allred_adamw_hyper* __restrict__ hyper, int ngroups,
                                          const float* __restrict__ norm_sq, float* info, const Scales& scale_rows = Scales{},
-                                         uint32_t sign_mask = 0) {
-    constexpr bool RHT = OUT == kOutMx4RhtFloor || OUT == kOutMx4RhtRceil;   // the rotation in front of the MXFP4 stage
-    constexpr bool MX4 = OUT == kOutMx4Floor || OUT == kOutMx4Rceil || RHT;
+                                         uint32_t sign_mask = 0, const allred_mx_sr_state* __restrict__ sr = nullptr,
+                                         uint32_t first_bucket = 0) {
+    constexpr bool SR = OUT == kOutMx4SrFloor || OUT == kOutMx4SrRceil || OUT == kOutMx4SrRhtFloor || OUT == kOutMx4SrRhtRceil;
+    // the rotation in front of the MXFP4 stage
+    constexpr bool RHT = OUT == kOutMx4RhtFloor || OUT == kOutMx4RhtRceil || OUT == kOutMx4SrRhtFloor || OUT == kOutMx4SrRhtRceil;
+    constexpr bool MX4 = OUT == kOutMx4Floor || OUT == kOutMx4Rceil || RHT || SR;
     constexpr bool MX = OUT != kOutBf16;   // any MX row format: element rows in bytes, and scale rows
-    constexpr bool RCEIL = OUT == kOutMxRceil || OUT == kOutMx4Rceil || OUT == kOutMx4RhtRceil;
+    constexpr bool RCEIL = OUT == kOutMxRceil || OUT == kOutMx4Rceil || OUT == kOutMx4RhtRceil || OUT == kOutMx4SrRceil ||
+                           OUT == kOutMx4SrRhtRceil;
     // TV: lanes of a row's run; RPI: rows per store instruction; W: waves with rows (MX4 at P = 8: two)
     constexpr int TV = MX4 ? 16 : 32, RPI = 64 / TV, W = (MX4 && P / RPI < 4) ? P / RPI : 4, RPW = P / W, OPS = RPW / RPI;
     constexpr int SC = MX4 ? 32 : 64;   // the slot's dword that holds the tile's scale bytes
@@ -253,6 +281,10 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
     // RHT only; filled under if constexpr: computed in every form, and dead there, it moved the MX forms' registers
     RhtLane<4> rl;
     if constexpr (RHT) rl = rht_lane<4>(sign_mask, lane & 7);
+    // SR only, under if constexpr for the same reason: the key and the step, and the tile's four words
+    SrCall sr_state;
+    SrWords rnd;
+    if constexpr (SR) sr_state = sr_call(sr);
     struct Tile {
         uint16_t* ranks;   // the bucket's row 0
         uint64_t stride;
@@ -411,7 +443,10 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
             if constexpr (RCEIL) sb += (A & 0x7fffffu) > (MX4 ? 0x400000u : 0x600000u) ? 1 : 0;
             sb = sb > 0 ? sb : 0;
             const float inv = __uint_as_float((uint32_t)(254 - sb) << 23);
-            if constexpr (MX4) {
+            if constexpr (SR) {
+                const uint32_t e = sr4_fp4(y.p, inv, rnd);
+                reinterpret_cast<uint16_t*>(&slot[j & 1][0])[lane] = (uint16_t)(special ? 0u : e);
+            } else if constexpr (MX4) {
                 uint32_t e = cvt2_fp4<0>(y.p[0] * inv, y.p[1] * inv, 0u);
                 e = cvt2_fp4<1>(y.p[2] * inv, y.p[3] * inv, e);   // bits 31:16 stay zero
                 reinterpret_cast<uint16_t*>(&slot[j & 1][0])[lane] = (uint16_t)(special ? 0u : e);
@@ -448,6 +483,13 @@ __device__ __forceinline__ void adamw_ag(const GroupSpan& span, const AdamwGroup
         New y{};
         if (w == 0) {
             if constexpr (NEXT) xn = load(nxt);
+            if constexpr (SR) {
+                // cur.v0 / TV: the tile's index in the rank row; 64 times it has no low six bits, so the lane adds without a carry
+                const uint64_t tile = cur.v0 / TV;
+                __builtin_amdgcn_sched_barrier(0);   // the next tile's loads are out
+                rnd = sr_words(sr_state, ((uint32_t)tile << 6) + (uint32_t)lane, (uint32_t)(tile >> 26), first_bucket + cur.bucket);
+                __builtin_amdgcn_sched_barrier(0);   // the wait for this tile's planes stands behind the words
+            }
             y = update(xc, j, (int)cur.group);
         }
         lds_barrier();   // wave 0's LDS write has landed (lgkmcnt(0)) before it arrives

@@ -96,6 +96,29 @@ inline bool adamw_mx_lists_disjoint(const AdamwMxRange* list, int count, uint64_
     return true;
 }
 
+// allred_plan_adamw_all_gather_shards_mxfp4_sr reads one more small device buffer (its allred_mx_sr_state): true
+// when [p, p + bytes) lies in the address space and shares no byte with an element row interval, a scale row
+// interval or a plane block of the list, nor with info's 16 bytes — what the call writes; hyper and norm_sq are
+// only read, the buffer may lie next to them.  The list has passed adamw_mx_lists_disjoint.
+inline bool adamw_mx_small_disjoint(const AdamwMxRange* list, int count, uint64_t total, const void* p, uint64_t bytes,
+                                    const void* info) {
+    const uint64_t lo = (uint64_t)(uintptr_t)p, ilo = (uint64_t)(uintptr_t)info;
+    uint64_t hi;
+    if (__builtin_add_overflow(lo, bytes, &hi) || hi > (uint64_t)UINTPTR_MAX) return false;
+    if (!bytes) return true;
+    if (info && lo < ilo + kAdamwInfoBytes && ilo < hi) return false;
+    if (count > 0 && (!list || total == 0)) return false;
+    for (int i = 0; i < count; ++i) {
+        const AdamwMxRange& s = list[i];
+        if (shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{s.rows, s.row_stride / 2, 0, nullptr, 0}, total) ||
+            shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{s.scales, s.scale_stride / 2, 0, nullptr, 0}, total))
+            return false;
+        for (const void* q : s.plane)
+            if (shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{nullptr, 0, s.n, q, s.shard_stride}, total)) return false;
+    }
+    return true;
+}
+
 // The argument rules of the call that need no plan, as engine.cpp adamw_mx_check applies them (plain
 // C++, so that tests/test_adamw_mx_ranges.py can hold every one of them without a device).
 enum AdamwMxVerdict { kAdamwMxOk = 0, kAdamwMxArg, kAdamwMxUnsupported };

@@ -1180,6 +1180,25 @@ int allred_plan_all_gather_shards_mxfp4_rht(allred_plan* p, const allred_mx_buck
     return launch_ag_group_mxfp4_rht(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, sign_mask, stream);
 }
 
+// allred_plan_all_gather_shards_mxfp4's checks with the rotate bit taken out of the flags first, then sr's own:
+// there, 8-byte aligned, and its 16 bytes off every row the call writes; all of it before any HIP call
+int allred_plan_all_gather_shards_mxfp4_sr(allred_plan* p, const allred_mx_bucket_f32* buckets, int count, int flags,
+                                           uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream) {
+    if (!sr || (uintptr_t)sr % 8) return ALLRED_ERR_ARG;
+    const int st = mx_check(p, buckets, count, flags & ~ALLRED_MX_SR_ROTATE, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    std::vector<MxRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_mx_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = MxRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.elems_per_rank, b.shard, b.shard_stride};
+    }
+    if (!mx_small_disjoint(ranges.data(), count, (uint64_t)p->total, sr, sizeof(allred_mx_sr_state))) return ALLRED_ERR_ARG;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp4_sr(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0, (flags & ALLRED_MX_SR_ROTATE) != 0,
+                                    sign_mask, sr, stream);
+}
+
 int allred_plan_all_gather_shards_mxfp8_2d(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,
                                            void* stream) {
     const int st = mx2d_check(p, buckets, count, flags);
@@ -1346,6 +1365,31 @@ int allred_plan_adamw_all_gather_shards_mxfp4_rht(allred_plan* p, const allred_a
     return launch_adamw_group_mxfp4_rht(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
                                         (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0, sign_mask,
                                         stream);
+}
+
+// allred_plan_adamw_all_gather_shards_mxfp4's checks with the rotate bit taken out of the flags first, then sr's
+// own: there, 8-byte aligned, and its 16 bytes off everything the call writes; all of it before any HIP call
+int allred_plan_adamw_all_gather_shards_mxfp4_sr(allred_plan* p, const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of,
+                                                 int count, const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq,
+                                                 float* info, int flags, uint32_t sign_mask, const allred_mx_sr_state* sr,
+                                                 void* stream) {
+    if (!sr || (uintptr_t)sr % 8) return ALLRED_ERR_ARG;
+    if (!adamw_groups_ok(group_of, count, ngroups)) return ALLRED_ERR_ARG;
+    const int st = adamw_mx_check(p, buckets, count, hyper, norm_sq, info, flags & ~ALLRED_ADAMW_MX_ROTATE, /*dry=*/false,
+                                  kAdamwHyperBytes * (uint64_t)ngroups, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0) return st;
+    std::vector<AdamwMxRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_adamw_mx_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = AdamwMxRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.elems_per_rank,
+                                         {b.param, b.grad, b.exp_avg, b.exp_avg_sq}, b.shard_stride};
+    }
+    if (!adamw_mx_small_disjoint(ranges.data(), count, (uint64_t)p->total, sr, sizeof(allred_mx_sr_state), info)) return ALLRED_ERR_ARG;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_adamw_group_mxfp4_sr(buckets, group_of, count, p->total, hyper, ngroups, norm_sq, info,
+                                       (flags & ALLRED_ADAMW_ZERO_GRAD) != 0, (flags & ALLRED_ADAMW_MX_RCEIL) != 0,
+                                       (flags & ALLRED_ADAMW_MX_ROTATE) != 0, sign_mask, sr, stream);
 }
 
 // The group rules first, then adamw_mx2d_check with the whole hyper array as hyper's interval; all of it

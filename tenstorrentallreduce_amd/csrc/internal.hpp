@@ -134,6 +134,11 @@ int launch_ag_group_mxfp4(const allred_mx_bucket_f32* buckets, int count, int to
 // (sign_mask, then the 32-point Hadamard transform) in front of the MXFP4 quantiser — k_ag_group_mxfp4_rht —,
 // batched as launch_ag_group_mxfp4 batches; no dry form: that call's launch count holds.
 int launch_ag_group_mxfp4_rht(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, uint32_t sign_mask, void* stream);
+// The same list through allred_plan_all_gather_shards_mxfp4_sr (mx4_sr_kernels.hip): the MXFP4 quantiser with
+// stochastic rounding (Philox4x32-10; seed and step read from sr, device memory), behind the rotation where
+// `rotate` — k_ag_group_mxfp4_sr —, batched as launch_ag_group_mxfp4 batches; no dry form.
+int launch_ag_group_mxfp4_sr(const allred_mx_bucket_f32* buckets, int count, int total, bool rceil, bool rotate,
+                             uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream);
 // a list of (checked) buckets of one fp32 matrix each (mx2d_kernels.hip): the shard quantised to MXFP8
 // both row-wise (where a bucket has rows) and column-wise, as W^T, into every rank's rows —
 // k_ag_group_mxfp8_2d —, ALLRED_MX2D_GROUP_MAX buckets per launch.  rceil, dry: as above.
@@ -159,6 +164,12 @@ int launch_adamw_group_mxfp4(const allred_adamw_mx_bucket_f32* buckets, const ui
 int launch_adamw_group_mxfp4_rht(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
                                  const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
                                  bool rceil, uint32_t sign_mask, void* stream);
+// The same list through allred_plan_adamw_all_gather_shards_mxfp4_sr (adamw_mx4_sr_kernels.hip): the same update,
+// p' (rotated where `rotate`) rounded stochastically to MXFP4 — k_adamw_ag_mxfp4_sr —, batched as
+// launch_adamw_group_mxfp4 batches; no dry form.
+int launch_adamw_group_mxfp4_sr(const allred_adamw_mx_bucket_f32* buckets, const uint8_t* group_of, int count, int total,
+                                const allred_adamw_hyper* hyper, int ngroups, const float* norm_sq, float* info, bool zero_grad,
+                                bool rceil, bool rotate, uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream);
 // a list of (checked) buckets of one fp32 matrix each, held as four planes (adamw_mx2d_kernels.hip):
 // launch_adamw_group_mxfp8's update, p' quantised to MXFP8 both row-wise (where a bucket has rows) and
 // column-wise into every rank's rows — k_adamw_ag_mxfp8_2d —, ALLRED_ADAMW_MX2D_GROUP_MAX buckets per launch.

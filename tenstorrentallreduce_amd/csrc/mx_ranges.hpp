@@ -28,6 +28,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "shard_f32_norm_ranges.hpp"
 #include "shard_ranges.hpp"
 
 namespace tsa {
@@ -68,6 +69,26 @@ inline bool mx_lists_disjoint(const MxRange* list, int count, uint64_t total, ui
     std::vector<ShardRange> ranges;
     if (!mx_as_ranges(list, count, &ranges, per_byte)) return false;
     return shard_lists_disjoint(ranges.data(), (int)ranges.size(), total);
+}
+
+// allred_plan_all_gather_shards_mxfp4_sr reads a small device buffer (its allred_mx_sr_state) while it writes the
+// rows: true when [p, p + bytes) lies in the address space and shares no byte with an element row interval or a
+// scale row interval of the list — shard_f32_norm_ranges.hpp's test, as adamw_mx_lists_disjoint applies it to
+// hyper.  The shard is only read: the buffer may lie next to it or in it.  The list has passed
+// mx_lists_disjoint (no product wraps); an empty interval collides with nothing.
+inline bool mx_small_disjoint(const MxRange* list, int count, uint64_t total, const void* p, uint64_t bytes) {
+    const uint64_t lo = (uint64_t)(uintptr_t)p;
+    uint64_t hi;
+    if (__builtin_add_overflow(lo, bytes, &hi) || hi > (uint64_t)UINTPTR_MAX) return false;
+    if (!bytes) return true;
+    if (count > 0 && (!list || total == 0)) return false;
+    for (int i = 0; i < count; ++i) {
+        const MxRange& s = list[i];
+        if (shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{s.rows, s.row_stride / 2, 0, nullptr, 0}, total) ||
+            shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{s.scales, s.scale_stride / 2, 0, nullptr, 0}, total))
+            return false;
+    }
+    return true;
 }
 
 // The argument rules of the call that need no plan, as engine.cpp mx_check applies them (plain C++,
