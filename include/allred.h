@@ -961,6 +961,49 @@ int allred_plan_all_gather_shards_mxfp8_2d_launches(const allred_plan* plan, con
 int allred_plan_all_gather_shards_mxfp4_2d(allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count, int flags,
                                            void* stream);
 int allred_plan_all_gather_shards_mxfp4_2d_launches(const allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count);
+/* 2D MXFP4 ALL-GATHER WITH STOCHASTICALLY ROUNDED, OPTIONALLY ROTATED COLUMN-WISE ROWS:
+ * allred_plan_all_gather_shards_mxfp4_2d whose t rows — the operand of the backward GEMM dX = dY W, the one
+ * allred_plan_all_gather_shards_mxfp4_sr's rounding and rotation exist for — are rounded as that call rounds, in
+ * the launch that writes the forward operand next to them.  No fp32 W^T has to exist and no pass runs over every
+ * rank's copy.  The bucket list, the accepted plans, the shape rules (cols % 32 == 0, nrows % (32 * total) == 0,
+ * total >= 8), the layout of all four outputs and count == 0 are allred_plan_all_gather_shards_mxfp4_2d's; the
+ * state and its semantics are allred_plan_all_gather_shards_mxfp4_sr's (16 bytes of DEVICE memory, 8-byte aligned,
+ * read by a wave-uniform load inside the kernel: a call captured ONCE follows `step` rewritten between replays).
+ * flags: ALLRED_MX_SCALE_RCEIL (bit 0) and ALLRED_MX_SR_ROTATE (bit 1); every other bit is refused, and the older
+ * 2D calls keep refusing bit 1.  Without ALLRED_MX_SR_ROTATE sign_mask is ignored; with it every value is valid.
+ * The kernel traces as k_ag_group_mxfp4_2d_sr<P, false|true, false|true, false|true> (csrc/mx4_2d_sr_kernels.hip;
+ * the bools: RCEIL, a bucket of the launch has rows, ROTATE).  No reference counterpart, no tune key; pipe_grid
+ * caps the grid.
+ * SEMANTICS.  Every output bit is a function of the input bits, the flags, sign_mask and the state.
+ *   ROW-WISE, when rows != NULL: rows and scales receive bit for bit what allred_plan_all_gather_shards_mxfp4_2d
+ *   writes for the same shard and ALLRED_MX_SCALE_RCEIL: round to nearest even, NOT rotated — the forward operand.
+ *   COLUMN-WISE, always: the t rows and t scale rows receive bit for bit what
+ *   allred_plan_all_gather_shards_mxfp4_sr would write, with the same flags, sign_mask and state, from a shard
+ *   holding W^T[cols][nrows], the bucket standing at the same index of the caller's list.  Spelt out: for column j
+ *   and row group g the MX block is x_k = W[32 g + k][j], k = 0 .. 31.  With ALLRED_MX_SR_ROTATE, THE ROTATION above
+ *   runs on it — the signs by sign_mask, the stages h = 1, 2, 4, 8, 16 in order, ONE multiply by 0x3E3504F3.  Then A,
+ *   the NaN / Inf block (scale 0xFF over sixteen 0x00 bytes), X, the scale byte and y_k = x_k * 2^(-X) of the MXFP4
+ *   rule; then THE SR RULE above with e = j * nrows + 32 g + k, the element's position in the t row: counter
+ *   (e / 4 & 0xffffffff, e / 4 >> 32, the bucket's index in the CALLER's list, step), word e % 4, key from seed.
+ *   The nibble goes to element e of EVERY rank's t row (byte e / 2, bits 3:0 for even e), the scale byte to byte
+ *   j * (nrows / 32) + g of EVERY rank's t scale row.
+ * The bits depend on neither P, the launch batching, the grid nor the shape of the kernel's work units.  Per rank
+ * only the bytes allred_plan_all_gather_shards_mxfp4_2d writes are written; the shard and the state are only read.
+ * CHECKS, all before any HIP call (a refused call writes nothing): ALLRED_ERR_ARG for sr NULL or
+ * (uintptr_t)sr % 8 != 0 and for a flag bit beyond bits 0 and 1; then those of allred_plan_all_gather_shards_mxfp4_2d,
+ * statuses as there; then ALLRED_ERR_ARG for the WHOLE list if [sr, sr + 16) shares a byte with any of a bucket's
+ * output intervals — [rows, + total * row_stride) and [scales, + total * scale_stride) where given,
+ * [t_rows, + total * t_row_stride), [t_scales, + total * t_scale_stride) (csrc/mx2d_ranges.hpp mx2d_small_disjoint).
+ * The state may lie next to a shard block or inside one.
+ * LAUNCHES: ONE launch covers ALLRED_MX4_2D_SR_GROUP_MAX = 20 buckets in list order — the RNE call's 96 bytes of
+ * table per bucket plus the state's address, sign_mask and the launch's first list index: 4000 bytes of kernel
+ * arguments, and a 21st bucket would reach 4 KiB.  allred_plan_all_gather_shards_mxfp4_2d_sr_launches returns
+ * ceil(count / 20), or a negative status for a list the call would refuse (it takes no state and checks none).
+ * The tables travel by value, so the call can be captured into a graph. */
+#define ALLRED_MX4_2D_SR_GROUP_MAX 20   /* buckets one launch of allred_plan_all_gather_shards_mxfp4_2d_sr covers */
+int allred_plan_all_gather_shards_mxfp4_2d_sr(allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count,
+                                              int flags, uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream);
+int allred_plan_all_gather_shards_mxfp4_2d_sr_launches(const allred_plan* plan, const allred_mx2d_bucket_f32* buckets, int count);
 /* ADAMW INSIDE THE MXFP8 ALL-GATHER: allred_plan_adamw_all_gather_shards_f32_groups with the rows of
  * allred_plan_all_gather_shards_mxfp8 — the MXFP8 training step in TWO launches
  * (allred_plan_reduce_scatter_shards_f32_norm, then this call), as the bf16 step is.  p' is quantised

@@ -690,6 +690,28 @@ class Plan:
             raise AllredError(st, "plan_all_gather_shards_mxfp4_2d_launches")
         return st
 
+    def all_gather_shards_mxfp4_2d_sr(self, buckets, sr_ptr, sign_mask=None, rceil: bool = False, stream=None) -> None:
+        """allred_plan_all_gather_shards_mxfp4_2d_sr: all_gather_shards_mxfp4_2d whose COLUMN-WISE rows — the operand
+        of dX = dY W — are rounded stochastically, behind the random Hadamard rotation where sign_mask is not None:
+        bit for bit what all_gather_shards_mxfp4_sr(sr_ptr, sign_mask, rceil) writes from a shard holding W^T, the
+        bucket at the same list index.  rows / scales (where given) stay what all_gather_shards_mxfp4_2d writes: RNE,
+        unrotated.  sr_ptr: all_gather_shards_mxfp4_sr's 16 bytes of device memory; a captured call follows `step`
+        rewritten there.  The host rule for the t rows: mxfp4_sr_quantize(W.T.ravel(), seed, step, index, rceil,
+        sign_mask).  One launch per ALLRED_MX4_2D_SR_GROUP_MAX buckets."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        flags = (_lib.MX_SCALE_RCEIL if rceil else 0) | (0 if sign_mask is None else _lib.MX_SR_ROTATE)
+        check(lib.allred_plan_all_gather_shards_mxfp4_2d_sr(self._h, arr, count, flags, int(sign_mask or 0) & 0xFFFFFFFF,
+                                                            int(sr_ptr or 0) or None, _stream_ptr(stream)),
+              "plan_all_gather_shards_mxfp4_2d_sr")
+
+    def shards_mxfp4_2d_sr_launches(self, buckets) -> int:
+        """Kernel launches all_gather_shards_mxfp4_2d_sr would enqueue for the list: one per ALLRED_MX4_2D_SR_GROUP_MAX buckets."""
+        arr, count = self._mx2d_buckets_f32(buckets)
+        st = lib.allred_plan_all_gather_shards_mxfp4_2d_sr_launches(self._h, arr, count)
+        if st < 0:
+            raise AllredError(st, "plan_all_gather_shards_mxfp4_2d_sr_launches")
+        return st
+
     @staticmethod
     def _adamw_mx_buckets_f32(buckets):
         """a sequence of (rows_ptr, row_stride, scales_ptr, scale_stride, elems_per_rank, param_ptr, grad_ptr,

@@ -170,7 +170,7 @@ class MxBucketF32(C.Structure):   # allred_mx_bucket_f32: e4m3 element rows, E8M
 
 MX_GROUP_MAX = 32     # ALLRED_MX_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8 covers
 MX_SCALE_RCEIL = 1    # ALLRED_MX_SCALE_RCEIL: its flags bit 0
-MX_SR_ROTATE = 2      # ALLRED_MX_SR_ROTATE: flags bit 1 of allred_plan_all_gather_shards_mxfp4_sr alone
+MX_SR_ROTATE = 2      # ALLRED_MX_SR_ROTATE: flags bit 1 of allred_plan_all_gather_shards_mxfp4_sr and ..._mxfp4_2d_sr alone
 
 
 class Mx2dBucketF32(C.Structure):   # allred_mx2d_bucket_f32: MxBucketF32's rows and scales (both may be NULL), the rows of W^T, the matrix
@@ -181,6 +181,7 @@ class Mx2dBucketF32(C.Structure):   # allred_mx2d_bucket_f32: MxBucketF32's rows
 
 MX2D_GROUP_MAX = 21   # ALLRED_MX2D_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp8_2d covers
 MX4_2D_GROUP_MAX = 21   # ALLRED_MX4_2D_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp4_2d covers
+MX4_2D_SR_GROUP_MAX = 20   # ALLRED_MX4_2D_SR_GROUP_MAX: buckets one launch of allred_plan_all_gather_shards_mxfp4_2d_sr covers
 
 
 class AdamwMxBucketF32(C.Structure):   # allred_adamw_mx_bucket_f32: MxBucketF32's rows and scales, AdamwBucketF32's four planes
@@ -276,6 +277,8 @@ SIGNATURES = [
     ("allred_plan_all_gather_shards_mxfp8_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_all_gather_shards_mxfp4_2d", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, _P]),
     ("allred_plan_all_gather_shards_mxfp4_2d_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
+    ("allred_plan_all_gather_shards_mxfp4_2d_sr", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int, C.c_int, C.c_uint32, _P, _P]),
+    ("allred_plan_all_gather_shards_mxfp4_2d_sr_launches", C.c_int, [_P, C.POINTER(Mx2dBucketF32), C.c_int]),
     ("allred_plan_adamw_all_gather_shards_mxfp8", C.c_int,
      [_P, C.POINTER(AdamwMxBucketF32), C.POINTER(C.c_uint8), C.c_int, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("allred_plan_adamw_shards_mxfp8_launches", C.c_int, [_P, C.POINTER(AdamwMxBucketF32), C.c_int]),

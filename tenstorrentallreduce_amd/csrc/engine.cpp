@@ -1079,6 +1079,23 @@ int mx2d_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int 
     }
 }
 
+// The checks of allred_plan_all_gather_shards_mxfp4_2d_sr, all before any HIP call: sr there and 8-byte aligned
+// (dry, the launch count's query: there is no sr), mx2d_check with the MXFP4 payload and the rotate bit taken out
+// of the flags first, then sr's 16 bytes off all four output intervals of every bucket (mx2d_small_disjoint).
+int mx2d_sr_check(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags, const allred_mx_sr_state* sr,
+                  bool dry) {
+    if (!dry && (!sr || (uintptr_t)sr % 8)) return ALLRED_ERR_ARG;
+    const int st = mx2d_check(p, buckets, count, flags & ~ALLRED_MX_SR_ROTATE, /*per_byte=*/2);
+    if (st != ALLRED_OK || count == 0 || dry) return st;
+    std::vector<Mx2dRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const allred_mx2d_bucket_f32& b = buckets[i];
+        ranges[(size_t)i] = Mx2dRange{b.rows, b.row_stride, b.scales, b.scale_stride, b.t_rows, b.t_row_stride, b.t_scales,
+                                      b.t_scale_stride, b.elems_per_rank, b.cols, b.shard, b.shard_stride};
+    }
+    return mx2d_small_disjoint(ranges.data(), count, (uint64_t)p->total, sr, sizeof(allred_mx_sr_state)) ? ALLRED_OK : ALLRED_ERR_ARG;
+}
+
 // The checks of allred_plan_adamw_all_gather_shards_mxfp8, all before any HIP call: the flags and
 // hyper, norm_sq and info — there where required, aligned —; the plan and the count as
 // shards_f32_check has them; then adamw_mx_ranges.hpp's rules for the list: rows and scales as
@@ -1227,6 +1244,22 @@ int allred_plan_all_gather_shards_mxfp4_2d_launches(const allred_plan* p, const 
     const int st = mx2d_check(p, buckets, count, 0, /*per_byte=*/2);
     if (st != ALLRED_OK || count == 0) return st;
     return launch_ag_group_mxfp4_2d(buckets, count, p->total, false, /*dry=*/true, nullptr);
+}
+
+int allred_plan_all_gather_shards_mxfp4_2d_sr(allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count, int flags,
+                                              uint32_t sign_mask, const allred_mx_sr_state* sr, void* stream) {
+    const int st = mx2d_sr_check(p, buckets, count, flags, sr, /*dry=*/false);
+    if (st != ALLRED_OK || count == 0) return st;
+    DeviceGuard guard(p->desc.device);
+    if (!guard.ok) return ALLRED_ERR_HIP;
+    return launch_ag_group_mxfp4_2d_sr(buckets, count, p->total, (flags & ALLRED_MX_SCALE_RCEIL) != 0,
+                                       (flags & ALLRED_MX_SR_ROTATE) != 0, sign_mask, sr, /*dry=*/false, stream);
+}
+
+int allred_plan_all_gather_shards_mxfp4_2d_sr_launches(const allred_plan* p, const allred_mx2d_bucket_f32* buckets, int count) {
+    const int st = mx2d_sr_check(p, buckets, count, 0, nullptr, /*dry=*/true);
+    if (st != ALLRED_OK || count == 0) return st;
+    return launch_ag_group_mxfp4_2d_sr(buckets, count, p->total, false, false, 0, nullptr, /*dry=*/true, nullptr);
 }
 
 int allred_plan_reduce_scatter_shards(allred_plan* p, const allred_shard_bucket* buckets, int count, void* stream) {

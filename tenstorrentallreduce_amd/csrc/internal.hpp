@@ -147,6 +147,11 @@ int launch_ag_group_mxfp8_2d(const allred_mx2d_bucket_f32* buckets, int count, i
 // MXFP4, two e2m1 elements per byte, in strips across shard blocks — k_ag_group_mxfp4_2d —,
 // ALLRED_MX4_2D_GROUP_MAX buckets per launch.
 int launch_ag_group_mxfp4_2d(const allred_mx2d_bucket_f32* buckets, int count, int total, bool rceil, bool dry, void* stream);
+// The same list through allred_plan_all_gather_shards_mxfp4_2d_sr (mx4_2d_sr_kernels.hip): the row-wise rows as
+// above, the column-wise rows rounded stochastically (seed and step read from sr, device memory), behind the
+// rotation where `rotate` — k_ag_group_mxfp4_2d_sr —, ALLRED_MX4_2D_SR_GROUP_MAX buckets per launch.
+int launch_ag_group_mxfp4_2d_sr(const allred_mx2d_bucket_f32* buckets, int count, int total, bool rceil, bool rotate,
+                                uint32_t sign_mask, const allred_mx_sr_state* sr, bool dry, void* stream);
 // a list of (checked) whole-tile buckets with their four fp32 planes, element rows and scale rows
 // (adamw_mx_kernels.hip): launch_adamw_group_f32's update with ngroups >= 1 parameter groups, p' quantised
 // to MXFP8 into every rank's rows — k_adamw_ag_mxfp8 —, ALLRED_ADAMW_MX_GROUP_MAX buckets per launch.  dry: as above.

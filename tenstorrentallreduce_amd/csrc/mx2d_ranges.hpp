@@ -69,6 +69,29 @@ inline bool mx2d_lists_disjoint(const Mx2dRange* list, int count, uint64_t total
     return shard_lists_disjoint(ranges.data(), (int)ranges.size(), total);
 }
 
+// allred_plan_all_gather_shards_mxfp4_2d_sr reads a small device buffer (its allred_mx_sr_state) while it writes up
+// to four row sets: true when [p, p + bytes) lies in the address space and shares no byte with any of a bucket's
+// output intervals — mx_small_disjoint (mx_ranges.hpp) with the two t intervals added, the row-wise pair only
+// where given.  The shard is only read: the buffer may lie next to it or in it.  The list has passed
+// mx2d_lists_disjoint (no product wraps); an empty interval collides with nothing.
+inline bool mx2d_small_disjoint(const Mx2dRange* list, int count, uint64_t total, const void* p, uint64_t bytes) {
+    const uint64_t lo = (uint64_t)(uintptr_t)p;
+    uint64_t hi;
+    if (__builtin_add_overflow(lo, bytes, &hi) || hi > (uint64_t)UINTPTR_MAX) return false;
+    if (!bytes) return true;
+    if (count > 0 && (!list || total == 0)) return false;
+    auto hits = [&](const void* rows, uint64_t stride) {
+        return rows && shard_f32_norm_detail::hits_bucket(lo, hi, ShardF32Range{rows, stride / 2, 0, nullptr, 0}, total);
+    };
+    for (int i = 0; i < count; ++i) {
+        const Mx2dRange& s = list[i];
+        if (hits(s.rows, s.row_stride) || hits(s.scales, s.scale_stride) || hits(s.t_rows, s.t_row_stride) ||
+            hits(s.t_scales, s.t_scale_stride))
+            return false;
+    }
+    return true;
+}
+
 // The argument rules of the call that need no plan, as engine.cpp mx2d_check applies them.
 enum Mx2dVerdict { kMx2dOk = 0, kMx2dArg, kMx2dUnsupported };
 

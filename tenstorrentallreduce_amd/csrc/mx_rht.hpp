@@ -1,7 +1,7 @@
-// mx_rht.hpp — the random Hadamard rotation of an MX block (allred.h, THE ROTATION), for the two kernels that
+// mx_rht.hpp — the random Hadamard rotation of an MX block (allred.h, THE ROTATION), for the kernels that
 // rotate the fp32 master values in the registers they already hold, in front of the MXFP4 quantiser
 // (mx4_rht_kernels.hip: k_ag_group_mxfp4_rht; adamw_mx4_rht_kernels.hip: k_adamw_ag_mxfp4_rht through
-// adamw_body.hpp).
+// adamw_body.hpp; the SR kernels, mx4_2d_sr_kernels.hip's column phase among them).
 //
 // The rule fixes every fp32 operation and its order: the sign flips, then the five butterfly stages
 // h = 1, 2, 4, 8, 16 — (x[i], x[i + h]) <- (x[i] + x[i + h], x[i] - x[i + h]) for (i & h) == 0 —, then ONE

@@ -1,7 +1,8 @@
-// mx_sr.hpp — the stochastic rounding of the MXFP4 quantiser (allred.h, THE SR RULE), for the two kernels that
+// mx_sr.hpp — the stochastic rounding of the MXFP4 quantiser (allred.h, THE SR RULE), for the kernels that
 // round the fp32 master values in the registers they already hold (mx4_sr_kernels.hip: k_ag_group_mxfp4_sr;
-// adamw_mx4_sr_kernels.hip: k_adamw_ag_mxfp4_sr through adamw_body.hpp): Philox4x32-10 and the integer
-// conversion of one scaled value to an e2m1 nibble.
+// adamw_mx4_sr_kernels.hip: k_adamw_ag_mxfp4_sr through adamw_body.hpp; mx4_2d_sr_kernels.hip:
+// k_ag_group_mxfp4_2d_sr, on the column-wise rows): Philox4x32-10 and the integer conversion of one scaled value
+// to an e2m1 nibble.
 //
 // The random word of an element depends on the seed, the step, the bucket's index in the caller's list and
 // the element's position in the gathered row — on indices alone, so a kernel generates a tile's words while
